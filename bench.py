@@ -8,6 +8,20 @@ resident in HBM before the timed region; actions come from a pre-generated
 device buffer of synthetic actions philox(seed, env, t) % 5 (4 B read per env-step).
 
   python bench.py [--gpus N --steps K --warmup W --envs E --grid G --rays C --range R]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, warm up, time
+the K steps, write the last step's outputs (--dump-outputs) and print the line.
+--full adds every secondary measurement to the line: the live roofline of the step
+kernel ("roofline"), the desynchronized window ("desync"), the gather-every-step leg
+("gather") and the CPU baseline ("cpu_baseline"); the paragraphs below describe them.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its
+caller -- obs f32 [n, 5C+27], reward f32 [n], terminated, truncated (0/1 as f32 [n])
+-- as DIR/obs.npy, reward.npy, terminated.npy, truncated.npy (above DUMP_MAX_BYTES a
+fixed, seeded sample of env rows, their indices in DIR/env_index.npy).  Maps, episodes
+and actions derive from --seed alone, so two runs with the same arguments write the
+same arrays.
 
 --gpus N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set)
 this process is one rank; run directly, it starts the N ranks itself
@@ -15,13 +29,13 @@ this process is one rank; run directly, it starts the N ranks itself
 exits with their status -- or exits non-zero at once if fewer than N GPUs are
 visible.  Each rank owns a disjoint shard of E envs (global ids rank*E ...), no
 collective on the data path ("scaling": "weak"); barrier + max-over-ranks
-timing.  `value` is that replica throughput.  Every run then also times the
+timing.  `value` is that replica throughput.  A --full run then also times the
 host-boundary leg of BASELINE config 5 ("with RCCL gather"): each step's packed
 (obs, reward, terminated, truncated) buffer gathered to rank 0 over RCCL,
 pipelined behind the next step (plantos_amd/shard.py step_gather) -- the line's
 "gather" object (with one rank there is nothing to gather and it says so).
 
-After the headline window the same batch is timed again with desynchronized
+After the headline window a --full run times the same batch again with desynchronized
 episodes (every env at its own step count: ~n/1000 auto-resets in every step, the
 steady state of a long training run); that result is the line's "desync" object.
 """
@@ -63,8 +77,15 @@ def parse():
     p.add_argument("--range", type=int, default=6)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--action-steps", type=int, default=64, help="distinct pre-generated action rows")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements: the live roofline of the step kernel, the "
+                        "desynchronized window, the gather-every-step leg and the CPU baseline (default: the "
+                        "headline window only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last timed step's outputs (obs, reward, terminated, "
+                        "truncated) as DIR/<name>.npy in float32")
     p.add_argument("--gather-steps", type=int, default=500,
-                   help="steps of the gather-every-step leg (RCCL gather of each step's outputs to rank 0, "
+                   help="--full: steps of the gather-every-step leg (RCCL gather of each step's outputs to rank 0, "
                         "pipelined; the line's 'gather' object; 0: skip it)")
     p.add_argument("--graph", type=int, default=64,
                    help="capture up to this many consecutive steps in one hipGraph and replay it (0: one host "
@@ -76,13 +97,13 @@ def parse():
                    help="time the desynchronized episode mix as the headline window (default: synchronized "
                         "fresh episodes, desync as the secondary 'desync' object)")
     p.add_argument("--desync-steps", type=int, default=20000,
-                   help="steps of the secondary desynchronized window (0: skip it)")
+                   help="--full: steps of the secondary desynchronized window (0: skip it)")
     p.add_argument("--desync-warmup", type=int, default=1300,
-                   help="untimed steps between desynchronizing and the secondary window (>= max_steps + the "
+                   help="--full: untimed steps between desynchronizing and the secondary window (>= max_steps + the "
                         "prefetch cadence: every env reset once and its next record generated)")
     p.add_argument("--prefetch-every", type=int, default=None,
                    help="steps between prefetched-reset launches (pe_config.prefetch_every; default: the library's)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--selftest", action="store_true",
                    help="launcher / rank plumbing only: gloo on the CPU, no GPU work (tests)")
@@ -331,6 +352,33 @@ def timed(torch, dist, device, K, one_step, chunk, graph, finish=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms = float(t[0]), float(t[1])
     return elapsed, kern_ms
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_SEED = 20240229  # of the env rows kept when the outputs are larger
+
+
+def dump_outputs(torch, b, directory, rank, world):
+    """--dump-outputs: the tensors the batch's last step() returned (they live in the
+    batch's io buffer until the next step) as float32 .npy files; a rank of a
+    multi-rank job writes <name>.rank<r>.npy.  Outputs above DUMP_MAX_BYTES: a sorted,
+    seeded sample of env rows (the same rows in every run), listed in env_index."""
+    import numpy as np
+    torch.cuda.synchronize()
+    n, D = b.num_envs, b.obs_dim
+    row_bytes = 4 * (D + 3) + 8  # obs + reward + terminated + truncated as f32, + an index
+    keep = None
+    if n * row_bytes > DUMP_MAX_BYTES:
+        g = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+        keep = torch.randperm(n, generator=g)[:DUMP_MAX_BYTES // row_bytes].sort().values
+    os.makedirs(directory, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, t in (("obs", b.obs), ("reward", b.reward), ("terminated", b.terminated), ("truncated", b.truncated)):
+        if keep is not None:
+            t = t[keep.to(t.device)]
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), t.to(torch.float32).cpu().numpy())
+    if keep is not None:
+        np.save(os.path.join(directory, f"env_index{suffix}.npy"), keep.numpy().astype(np.float64))
 
 
 def episodes(b):
@@ -690,6 +738,8 @@ def main():
         ep0 = episodes(b)
     elapsed, kern_ms = timed(torch, dist, device, K, one_step, chunk, graph)
     b.raise_on_errors()
+    if args.dump_outputs:  # before anything steps the batch again
+        dump_outputs(torch, b, args.dump_outputs, rank, world)
     resets = resets_since(torch, dist, b, ep0)
     total_steps = n * K * world
     value = total_steps / elapsed
@@ -698,17 +748,19 @@ def main():
     # the step kernel's launch duration back to back, live: HIP events over >= 2048 steps of
     # captured graphs after the timed window (a short window's events also hold the gap
     # before its first graph node: 20 steps 11.7 us against 9.45 us per kernel, r4)
-    ev_chunk = chunk if chunk >= 256 else 256
-    ev_graph = graph if ev_chunk == chunk else capture(ev_chunk)
-    kern_us_events = event_us(torch, ev_graph, max(1, 2048 // ev_chunk), ev_chunk)
-    if dist:
-        t = torch.tensor([kern_us_events], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        kern_us_events = float(t[0])
-    b.raise_on_errors()
+    kern_us_events = None
+    if args.full:
+        ev_chunk = chunk if chunk >= 256 else 256
+        ev_graph = graph if ev_chunk == chunk else capture(ev_chunk)
+        kern_us_events = event_us(torch, ev_graph, max(1, 2048 // ev_chunk), ev_chunk)
+        if dist:
+            t = torch.tensor([kern_us_events], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            kern_us_events = float(t[0])
+        b.raise_on_errors()
 
     desync = None
-    if args.desync_steps > 0 and not args.desync:
+    if args.full and args.desync_steps > 0 and not args.desync:
         desynchronize(torch, b, args.seed)
         Kd = args.desync_steps
         d_chunk = plan_graph(Kd, args.graph, pf)
@@ -733,7 +785,7 @@ def main():
 
     # BASELINE config 5's host-boundary leg (gather_leg)
     gather = None
-    if args.gather_steps > 0:
+    if args.full and args.gather_steps > 0:
         # its own shard (same global ids) whose step keeps the obs as byte codes where the
         # geometry has a byte-coded sector kernel (config 5's 20x20 / 16 rays does)
         try:
@@ -783,44 +835,49 @@ def main():
             ("resets_in_window" if ep_at == "window" else "resets_in_warmup_and_window"): resets,
             "lib_sha": sha,
         }
-        # roofline of the step kernel: algorithmic bytes x envs / its average launch
-        # duration measured live in THIS run (HIP events on the launch stream around >= 2048
-        # back-to-back graph-replayed steps); the committed rocprofv3 stats of this library
-        # and config are a cross-check only, flagged when they disagree by more than 5 %
-        rp = rocprof_kernel_ns(out["config"], sha)
-        k_us = kern_us_events
-        achieved = B * n / (k_us * 1e-6) / 1e9
-        rp_us = rp["ns"] / 1e3 if rp else None
-        out["roofline"] = {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBPS, "traffic": None, "bytes_per_env_step": B,
-            "kernel_us": k_us,
-            "kernel_us_source": "HIP events, >= 2048 back-to-back steps of captured graphs (this run)",
-            "kernel_us_rocprof": rp_us,
-            "kernel_us_rocprof_source": (f"committed rocprofv3 --kernel-trace --stats average of this library and "
-                                         f"config ({rp['source']})" if rp else None),
-            "rocprof_agrees": (abs(k_us - rp_us) <= 0.05 * rp_us) if rp else None,
-            "frac_rocprof": B * n / (rp_us * 1e-6) / 1e9 / HBM_PEAK_GBPS if rp else None,
-            "kernel_us_events": kern_us_events,
-            "frac_events": B * n / (kern_us_events * 1e-6) / 1e9 / HBM_PEAK_GBPS,
-            "kernel_us_window": kern_ms * 1e3, "frac_window": achieved_window / HBM_PEAK_GBPS,
-            "window_note": "kernel_us_window / frac_window: HIP events over the timed window itself (a short "
-                           "window adds the launch of its first graph node)"}
         if dist:
             out["config"]["rccl"] = nccl_version
-        tr = measured_traffic(out["config"], sha)
-        if tr is not None:
-            out["roofline"].update({"traffic": tr["traffic"], "traffic_raw": tr["traffic_raw"],
-                                    "traffic_all_reads_x2": tr["traffic_hi"], "traffic_source": tr["source"],
-                                    "traffic_calibration": tr["calibration"],
-                                    "traffic_per_env_step": tr["traffic"] / n})
-        else:
-            out["roofline"]["traffic_note"] = f"no committed PMC profile of this library (lib_sha {sha})"
+        window = {"kernel_us_window": kern_ms * 1e3, "frac_window": achieved_window / HBM_PEAK_GBPS,
+                  "window_note": "kernel_us_window / frac_window: HIP events over the timed window itself (a short "
+                                 "window adds the launch of its first graph node)"}
+        if args.full:
+            # roofline of the step kernel: algorithmic bytes x envs / its average launch
+            # duration measured live in THIS run (HIP events on the launch stream around >= 2048
+            # back-to-back graph-replayed steps); the committed rocprofv3 stats of this library
+            # and config are a cross-check only, flagged when they disagree by more than 5 %
+            rp = rocprof_kernel_ns(out["config"], sha)
+            k_us = kern_us_events
+            achieved = B * n / (k_us * 1e-6) / 1e9
+            rp_us = rp["ns"] / 1e3 if rp else None
+            out["roofline"] = {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBPS, "traffic": None, "bytes_per_env_step": B,
+                "kernel_us": k_us,
+                "kernel_us_source": "HIP events, >= 2048 back-to-back steps of captured graphs (this run)",
+                "kernel_us_rocprof": rp_us,
+                "kernel_us_rocprof_source": (f"committed rocprofv3 --kernel-trace --stats average of this library and "
+                                             f"config ({rp['source']})" if rp else None),
+                "rocprof_agrees": (abs(k_us - rp_us) <= 0.05 * rp_us) if rp else None,
+                "frac_rocprof": B * n / (rp_us * 1e-6) / 1e9 / HBM_PEAK_GBPS if rp else None,
+                "kernel_us_events": kern_us_events,
+                "frac_events": B * n / (kern_us_events * 1e-6) / 1e9 / HBM_PEAK_GBPS,
+                **window}
+            tr = measured_traffic(out["config"], sha)
+            if tr is not None:
+                out["roofline"].update({"traffic": tr["traffic"], "traffic_raw": tr["traffic_raw"],
+                                        "traffic_all_reads_x2": tr["traffic_hi"], "traffic_source": tr["source"],
+                                        "traffic_calibration": tr["calibration"],
+                                        "traffic_per_env_step": tr["traffic"] / n})
+            else:
+                out["roofline"]["traffic_note"] = f"no committed PMC profile of this library (lib_sha {sha})"
+        else:  # the timed window's own events only: the live kernel figure is a run of its own (--full)
+            out["roofline"] = {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s", "bytes_per_env_step": B,
+                               **window}
         if desync is not None:
             out["desync"] = desync
         if gather is not None:
             out["gather"] = gather
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, plants, obstacles)
         print(json.dumps(out), flush=True)
     b.close()

@@ -32,7 +32,7 @@ def test_torchrun_one_rank_rccl_bench_line():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", "1", "--envs", "4096", "--steps", "40", "--warmup", "5", "--desync-steps", "0",
+           "--gpus", "1", "--full", "--envs", "4096", "--steps", "40", "--warmup", "5", "--desync-steps", "0",
            "--gather-steps", "40", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -7,7 +7,7 @@ OUT=gpurun_out/stagger_geo.jsonl
 : > "$OUT"
 run() {  # tag stagger args...
   local tag=$1 st=$2; shift 2
-  PE_STAGGER=$st PLANTOS_HIP_LIB=$LIB timeout -k 10 150 python bench.py --no-cpu-baseline --desync-steps 0 \
+  PE_STAGGER=$st PLANTOS_HIP_LIB=$LIB timeout -k 10 150 python bench.py --full --no-cpu-baseline --desync-steps 0 \
     --gather-steps 0 "$@" | python3 -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print(json.dumps({'tag':'$tag','stagger':$st,'us':d['ms_per_step']*1e3,'frac':d['roofline']['frac']}))" >> "$OUT"
   tail -1 "$OUT"
 }

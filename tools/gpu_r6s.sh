@@ -9,11 +9,11 @@ one() {
   python3 -c "import json,sys; d=json.load(open('gpurun_out/s_one.json')); r=d['roofline']; print(json.dumps({'tag': sys.argv[1], 'us': d['ms_per_step']*1e3, 'window_events_us': r.get('kernel_us_window'), 'events_us': r['kernel_us_events'], 'launch': d['config']['launch']}))" $tag >> $OUT
 }
 for r in 1 2; do
-  one long_graph --steps 20000 --warmup 200
-  one long_direct --steps 20000 --warmup 200 --graph 0
+  one long_graph --full --steps 20000 --warmup 200
+  one long_direct --full --steps 20000 --warmup 200 --graph 0
 done
 for r in 1 2 3 4; do
-  one drv_graph --steps 20 --warmup 5
-  one drv_direct --steps 20 --warmup 5 --short-window direct
+  one drv_graph --full --steps 20 --warmup 5
+  one drv_direct --full --steps 20 --warmup 5 --short-window direct
 done
 cat $OUT

@@ -21,12 +21,12 @@ for w in "$@"; do
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1 ;;
     bench)
-      timeout -k 10 300 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err ;;
+      timeout -k 10 300 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err ;;
     benchd)
       timeout -k 10 300 python bench.py --desync --steps 20480 --warmup 200 --desync-steps 0 --gather-steps 0 --no-cpu-baseline \
         > $OUT/benchd_$TAG.json 2> $OUT/benchd_$TAG.err ;;
     bench64)
-      timeout -k 10 300 python bench.py --grid 64 --rays 64 --range 6 --steps 3000 --warmup 100 --desync-steps 3000 \
+      timeout -k 10 300 python bench.py --full --grid 64 --rays 64 --range 6 --steps 3000 --warmup 100 --desync-steps 3000 \
         --cpu-seconds 5 > $OUT/bench64_$TAG.json 2> $OUT/bench64_$TAG.err ;;
     stats)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats_$TAG -o run -- \
@@ -48,9 +48,9 @@ for w in "$@"; do
     stamps|stampsd)
       flag=""; [ $w = stampsd ] && flag="--desync"
       timeout -k 10 180 python tools/stamps.py run $flag > $OUT/${w}_$TAG.json 2> $OUT/${w}_$TAG.err ;;
-    benchx:*)  # benchx:<name>:<bench args with _ for spaces>
+    benchx:*)  # benchx:<name>:<bench args with _ for spaces>: a --full bench line of another geometry
       IFS=: read -r _ name args <<< "$w"
-      timeout -k 10 300 python bench.py ${args//_/ } > $OUT/benchx_${name}_$TAG.json 2> $OUT/benchx_${name}_$TAG.err ;;
+      timeout -k 10 300 python bench.py --full ${args//_/ } > $OUT/benchx_${name}_$TAG.json 2> $OUT/benchx_${name}_$TAG.err ;;
     statsx:*)  # statsx:<name>:<bench args with _ for spaces> under rocprofv3 --kernel-trace --stats
       IFS=: read -r _ name args <<< "$w"
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/statsx_${name}_$TAG -o run -- \
