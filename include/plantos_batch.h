@@ -18,6 +18,7 @@
  *   pe_seed         VecEnv.seed / reset(seed=...)    (the reference ignores it for maps)
  *   pe_destroy      PlantOSEnv.close                 plantos_env.py:522-528
  *   pe_mcts_*       MCTS.search for every env at once mcts_custom_trainer.py:72-243
+ *   pe_render       PlantOSEnvNew.render ('rgb_array') gradio-app/plantos_env_new.py:631-633
  *
  * Conventions
  *  - Every array argument is a DEVICE pointer (caller-owned, e.g. a torch tensor on
@@ -269,6 +270,40 @@ int pe_mcts_get_rng(pe_mcts* m, uint32_t* key, int32_t* pos);
  * -1 pad), visits i32[n,5], value f64[n,5].  Device pointers. */
 int pe_mcts_search(pe_mcts* m, const uint8_t* mask, int32_t* actions, int32_t* root_order, int32_t* root_visits,
                    double* root_value, void* stream);
+
+/* rgb_array frames (PlantOSEnvNew.render with render_mode='rgb_array',
+ * gradio-app/plantos_env_new.py:631-633, 697-762: the colour path taken when no sprite
+ * loads).  s = cell_size (the reference hard-codes 30, :112), H = W = G*s, a frame is
+ * u8 [H][W][3] RGB; image row <-> grid row x, image column <-> grid column y.  Layers,
+ * later over earlier: background; explored cells ((200,200,200, alpha 100) blended,
+ * per channel ((d<<8) + (s-d)*a + s) >> 8); obstacles; plants; the C LIDAR rays (the
+ * observation's march stopped by the map edge, an obstacle or any plant; end point
+ * centre + (int(h*s*sin a), int(h*s*cos a)); 1-px integer Bresenham line, both end
+ * points plotted, and a disc dx*dx + dy*dy <= 4 at the end; pixels off the canvas
+ * dropped); the rover cell; grid lines on pixel rows / columns j*s, j < G.  The full
+ * specification heads rl-env_amd/csrc/pe_render.hip.  Sprites, 'human' windows, the
+ * Ursina viewer and the root env's _render_2d are out of scope.
+ *
+ * pe_render_tables (host only, HOST pointers, either may be NULL): ray_ends
+ * i32[C][R+1][2] = (int(h*s*sin a), int(h*s*cos a)) for ray i (a = 2*pi*i/C), h = 0..R
+ * -- (column, row) pixel offsets from the rover cell's centre, h*s an integer product,
+ * the rest in double, truncated toward zero; palette u8[8][3] in the order
+ * background (34,139,34), explored (99,163,99), obstacle (105,105,105), thirsty
+ * (255,165,0), hydrated (0,255,0), ray (100,100,255), rover (0,0,255), grid line
+ * (200,200,200).  Only lidar_channels / lidar_range of `c` are read. */
+int pe_render_tables(const pe_config* c, int32_t cell_size, int32_t* ray_ends, uint8_t* palette);
+
+/* k frames: frame j shows env env_index[j] (i32[k], device), or env j when env_index is
+ * NULL (then k <= n_envs); it starts at out + j * frame_stride and its rows are
+ * row_stride bytes apart (row_stride >= 3W; frames of one mosaic row: frame_stride = 3W).
+ * Indices may repeat and come in any order; a frame whose index is outside [0, n_envs)
+ * is not written (nothing out of range is accessed).  Only the 3W bytes of the k frames'
+ * H rows are written.  2 <= cell_size <= 64 and G * cell_size <= 4096, else PE_ERR_ARG,
+ * as for k < 0 or bad strides.  The per-cell_size device table is built at the first
+ * call with that cell_size (a blocking upload into fresh memory) and kept until
+ * pe_destroy.  Reads the state only; asynchronous on `stream`. */
+int pe_render(pe_handle* h, int32_t k, const int32_t* env_index_or_null, int32_t cell_size, uint8_t* out,
+              int64_t frame_stride, int64_t row_stride, void* stream);
 
 /* Introspection for tests / benchmarks. */
 int32_t pe_num_envs(const pe_handle* h);

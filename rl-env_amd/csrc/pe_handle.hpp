@@ -35,6 +35,7 @@ struct pe_handle {
   int pf_every;      // steps between queue-mode prefetch launches (pe_config.prefetch_every)
   int pf_count;      // steps since the last one
   int pf_blocks;     // queue-mode prefetch grid: workgroups resident at once
+  void* render_cache;  // pe_render's per-cell_size device tables (pe_render.hip), or NULL
 };
 
 // pe_internal_set_error (plantos_batch.hip): records pe_last_error() for this thread.
@@ -42,3 +43,5 @@ extern "C" int pe_internal_set_error(int code, const char* msg);
 // pe_internal_flush_vx (plantos_batch.hip): the steps' deferred visit-overflow writes applied
 // on `stream` (before anything reads the exact visit counts, e.g. the MCTS clone).
 extern "C" int pe_internal_flush_vx(const pe_handle* h, void* stream);
+// pe_internal_render_free (pe_render.hip): frees the handle's render tables (pe_destroy).
+extern "C" void pe_internal_render_free(pe_handle* h);

@@ -3808,6 +3808,7 @@ int pe_destroy(pe_handle* h) {
   }
   if (h->cur_mem) (void)hipFree(h->cur_mem);
   if (h->pf_mem) (void)hipFree(h->pf_mem);
+  pe_internal_render_free(h);
   delete h;
   return rc;
 }

@@ -41,6 +41,7 @@ EXPORTS = [
     "pe_curriculum_enable", "pe_curriculum_disable", "pe_curriculum_get",
     "pe_mcts_create", "pe_mcts_destroy", "pe_mcts_seed", "pe_mcts_set_rng", "pe_mcts_get_rng", "pe_mcts_search",
     "pe_step_codes", "pe_obs_code_table", "pe_expand_obs_codes",
+    "pe_render_tables", "pe_render",
 ]
 
 
@@ -123,12 +124,15 @@ def lib():
     L.pe_mcts_set_rng.argtypes = [P, P, P]
     L.pe_mcts_get_rng.argtypes = [P, P, P]
     L.pe_mcts_search.argtypes = [P, P, P, P, P, P, P]
+    if hasattr(L, "pe_render"):  # (an older library loaded for a same-box A/B lacks them)
+        L.pe_render_tables.argtypes = [CP, I32, P, P]
+        L.pe_render.argtypes = [P, I32, P, I32, P, ctypes.c_int64, ctypes.c_int64, P]
     for name in ("pe_create", "pe_destroy", "pe_seed", "pe_reset", "pe_step", "pe_get_info", "pe_get_state",
                  "pe_set_state", "pe_load_maps", "pe_synth_actions", "pe_poll_errors", "pe_pystream_create",
                  "pe_pystream_next", "pe_pystream_destroy", "pe_curriculum_enable", "pe_curriculum_disable",
                  "pe_curriculum_get", "pe_mcts_create", "pe_mcts_destroy", "pe_mcts_seed", "pe_mcts_set_rng",
                  "pe_mcts_get_rng", "pe_mcts_search", "pe_step_codes", "pe_obs_code_table",
-                 "pe_expand_obs_codes"):
+                 "pe_expand_obs_codes", "pe_render_tables", "pe_render"):
         if hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
     _lib = L

@@ -313,6 +313,51 @@ class PlantOSBatch:
                     "pe_load_maps")
         return out
 
+    def render(self, env_index=None, cell_size=30, out=None):
+        """rgb_array frames of envs `env_index` (all envs when None; indices may repeat, in
+        any order): uint8 device tensor [k, H, W, 3], H = W = grid_size * cell_size -- the
+        fork's sprite-less PlantOSEnvNew.render() (gradio-app/plantos_env_new.py:631-633,
+        697-762; the reference's cell_size is 30), drawn by pe_render from the live state,
+        which it only reads.  A host-side `env_index` (list / numpy / CPU tensor) is checked
+        here (ValueError) and nothing is launched; an int32 tensor already on the device is
+        passed as it is (a frame with an out-of-range index is left unwritten).
+        out: a uint8 tensor [k, H, W, 3] on this device to draw into; pixels must be
+        contiguous (strides (.., .., 3, 1)), rows and frames may be strided -- e.g. the tiles
+        of one mosaic row, a permuted view of the canvas."""
+        n, s = self.num_envs, int(cell_size)
+        if s < 2:
+            raise ValueError(f"cell_size must be >= 2, got {cell_size}")
+        idx = None
+        if env_index is None:
+            k = n
+        else:
+            on_dev = (type(env_index) is torch.Tensor and env_index.is_cuda
+                      and env_index.get_device() == self._dev_index)
+            if not on_dev:
+                host = torch.as_tensor(env_index).reshape(-1).cpu()
+                if host.numel() and (host.dtype.is_floating_point or host.dtype is torch.bool):
+                    raise ValueError("env_index must hold integers")
+                if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n):
+                    raise ValueError(f"env_index out of range [0, {n})")
+                idx = host.to(device=self.device, dtype=torch.int32)
+            else:
+                idx = env_index.reshape(-1).to(torch.int32).contiguous()
+            k = idx.numel()
+        H = W = self.grid_size * s
+        if out is None:
+            out = torch.empty((k, H, W, 3), dtype=torch.uint8, device=self.device)
+        elif not (type(out) is torch.Tensor and out.dtype is torch.uint8 and out.is_cuda
+                  and out.get_device() == self._dev_index and tuple(out.shape) == (k, H, W, 3)
+                  and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) >= 3 * W
+                  and (k < 2 or out.stride(0) >= 3 * W)):
+            raise ValueError(f"out must be a uint8 tensor of shape {(k, H, W, 3)} on {self.device} with "
+                             "contiguous pixels (strides (>= 3W, >= 3W, 3, 1))")
+        self._idx_keep = idx  # alive until the launch has read it
+        with torch.cuda.device(self.device):
+            C.check(C.lib().pe_render(self.handle, k, _ptr(idx), s, _ptr(out), out.stride(0) if k > 1 else 0,
+                                      out.stride(1), self._stream()), "pe_render")
+        return out
+
     def synth_actions(self, seed, t, out=None):
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device) if out is None else out
         with torch.cuda.device(self.device):

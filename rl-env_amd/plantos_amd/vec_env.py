@@ -230,7 +230,8 @@ class PlantOSVecEnv(_VecEnvBase):
     def __init__(self, num_envs, grid_size=21, num_plants=8, num_obstacles=50, lidar_range=2, lidar_channels=10,
                  thirsty_plant_prob=0.7, max_steps=1000, seed=0, device=None, tensors=False, env_id_offset=0,
                  observation_mode="lidar", render_mode=None, batch=None, reset_mode="device", python_seed=None,
-                 curriculum=False, map_generation_algo="original", host_buffers=0, prefetch_every=None):
+                 curriculum=False, map_generation_algo="original", host_buffers=0, prefetch_every=None,
+                 render_envs=None, cell_size=30):
         """reset_mode="device": maps from the device generator keyed by (seed, env id,
         episode) -- the throughput mode.  reset_mode="cpython": the reference's own
         layouts, seed-exact: CPython's global `random` after random.seed(python_seed)
@@ -249,7 +250,13 @@ class PlantOSVecEnv(_VecEnvBase):
         enough for SB3's collect_rollouts with k >= 2); 0 (default): a fresh array
         per step, as DummyVecEnv returns.
         prefetch_every: pe_config.prefetch_every (steps between the launches that
-        generate next-episode maps ahead of time; None: the library's 256, 0: off)."""
+        generate next-episode maps ahead of time; None: the library's 256, 0: off).
+        render_mode="rgb_array": get_images() / render() draw the envs `render_envs`
+        (default: the first min(num_envs, 16) -- a departure from DummyVecEnv, which
+        renders every env: 65536 frames of 600 x 600 would be 70 GB) at `cell_size` pixels
+        per cell (the reference's 30) on the device (PlantOSBatch.render: the fork's
+        sprite-less frame).  Any other render_mode (None, 'human') keeps raising
+        NotImplementedError: windows, sprites and the 3D viewer are out of scope."""
         if observation_mode != "lidar":
             raise ValueError("only observation_mode='lidar' exists in the reference (plantos_env.py:27)")
         if reset_mode not in ("device", "cpython"):
@@ -276,6 +283,12 @@ class PlantOSVecEnv(_VecEnvBase):
         self.lidar_range, self.lidar_channels = lidar_range, lidar_channels
         self.thirsty_plant_prob, self.max_steps = thirsty_plant_prob, max_steps
         self.render_mode = render_mode
+        self.cell_size = int(cell_size)
+        idx = list(range(min(int(num_envs), 16))) if render_envs is None else [int(i) for i in render_envs]
+        if any(i < 0 or i >= int(num_envs) for i in idx):
+            raise ValueError(f"render_envs out of range [0, {int(num_envs)})")
+        self.render_envs = idx
+        self._render_idx = None  # device copy, made at the first frame
         self.tensors = bool(tensors)
         self.host_buffers = int(host_buffers)
         self._pinned_packed = None
@@ -483,11 +496,41 @@ class PlantOSVecEnv(_VecEnvBase):
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False for _ in self._indices(indices)]
 
+    def _check_render(self, mode):
+        if mode != "rgb_array":
+            raise NotImplementedError(f"render_mode={mode!r}: only 'rgb_array' frames are drawn (construct with "
+                                      "render_mode='rgb_array'); windows and the 3D viewer are out of scope")
+        if not hasattr(self.batch, "render"):
+            raise NotImplementedError("this batch has no render()")
+        if self._render_idx is None:
+            self._render_idx = torch.as_tensor(self.render_envs, dtype=torch.int32, device=self.batch.device)
+        return self._render_idx
+
     def get_images(self):
-        raise NotImplementedError("rendering is out of scope (SURVEY.md §2 row 2)")
+        """The frames of `render_envs`: a list of uint8 [H, W, 3] arrays, or (tensors=True)
+        one device tensor [k, H, W, 3]."""
+        idx = self._check_render(self.render_mode)
+        frames = self.batch.render(idx, self.cell_size)
+        return frames if self.tensors else list(frames.cpu().numpy())
 
     def render(self, mode=None):
-        raise NotImplementedError("rendering is out of scope (SURVEY.md §2 row 2)")
+        """The frames of `render_envs` tiled as SB3's VecEnv.render tiles them (tile_images):
+        rows = ceil(sqrt(k)), cols = ceil(k / rows), image i at tile (i // cols, i % cols),
+        missing tiles black; uint8 [rows*H, cols*W, 3] (numpy, or a device tensor with
+        tensors=True).  The kernel draws straight into the mosaic, one call per tile row."""
+        idx = self._check_render(self.render_mode if mode is None else mode)
+        k = len(self.render_envs)
+        rows = int(np.ceil(np.sqrt(k))) if k else 0
+        cols = int(np.ceil(k / rows)) if k else 0
+        H = W = self.grid_size * self.cell_size
+        canvas = torch.zeros((rows * H, cols * W, 3), dtype=torch.uint8, device=self.batch.device)
+        for r in range(rows):
+            i0, i1 = r * cols, min((r + 1) * cols, k)
+            if i0 >= i1:
+                break
+            tiles = canvas[r * H:(r + 1) * H, :(i1 - i0) * W].unflatten(1, (i1 - i0, W)).permute(1, 0, 2, 3)
+            self.batch.render(idx[i0:i1], self.cell_size, out=tiles)
+        return canvas if self.tensors else canvas.cpu().numpy()
 
 
 class PlantOSVectorEnv:
