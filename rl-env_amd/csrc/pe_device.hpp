@@ -424,23 +424,58 @@ __device__ __forceinline__ void img_set(uint64_t* sg, const Geo& g, int row, int
 
 // Index of the j-th real cell (row-major) whose code matches `kind`
 // (kind 0: not an obstacle, kind 1: empty).  Returns the cell id x*G+y.
-__device__ inline int img_nth_cell(const uint64_t* sg, const Geo& g, const Tables* tab, int j, int kind) {
-  for (int row = 0; row < g.G; ++row) {
-    for (int w = 0; w < g.WPR; ++w) {
-      const uint64_t v = sg[row * g.WPR + w];
-      const uint64_t lo = v & kEven64, hi = (v >> 1) & kEven64;
-      const uint64_t real = tab->grid_real[w];
-      uint64_t m = kind == 0 ? (real & ~(lo & ~hi)) : (real & ~(lo | hi));
-      const int c = __popcll(m);
-      if (j < c) {
-        for (int k = 0; k < j; ++k) m &= m - 1;
-        const int pcol = w * 32 + (__ffsll((unsigned long long)m) - 1) / 2;
-        return row * g.G + (pcol - g.R);
-      }
-      j -= c;
-    }
+// One lane per env runs this with a different j in every lane: the scan has no
+// data-dependent exit or trip count (a wave executes the union of its lanes' paths --
+// the early exit and a clear-lowest-bit loop of up to j turns cost a whole-batch reset
+// most of its time); the word holding the cell is picked by selects, the j-th set bit
+// in it by a popcount binary search.
+__device__ __forceinline__ int nth_even_bit(uint64_t m, int j) {  // position of the j-th (0-based) set bit; bits at even positions
+  int pos = 0;
+  int c = __popc((uint32_t)m);
+  if (j >= c) { j -= c; pos = 32; }
+  uint32_t h = (uint32_t)(m >> pos);
+  c = __popc(h & 0xFFFFu);
+  if (j >= c) { j -= c; pos += 16; h >>= 16; }
+  c = __popc(h & 0xFFu);
+  if (j >= c) { j -= c; pos += 8; h >>= 8; }
+  c = __popc(h & 0xFu);
+  if (j >= c) { j -= c; pos += 4; h >>= 4; }
+  if (j >= (int)(h & 1u)) pos += 2;
+  return pos;
+}
+// (row, col): the cell's real coordinates; false when no cell was selected.
+__device__ inline bool img_nth_rc(const uint64_t* sg, const Geo& g, const Tables* tab, int j, int kind, int& row_o,
+                                  int& col_o) {
+  const int G = g.G, WPR = g.WPR;
+  uint64_t msel = 0ull;
+  int rsel = 0, wsel = 0, jsel = 0;
+  auto scan = [&](int row, int w, uint64_t v, uint64_t real) {
+    const uint64_t lo = v & kEven64, hi = (v >> 1) & kEven64;
+    const uint64_t m = kind == 0 ? (real & ~(lo & ~hi)) : (real & ~(lo | hi));
+    const int c = __popcll(m);
+    const bool hit = (uint32_t)j < (uint32_t)c;  // (j < 0: found already)
+    msel = hit ? m : msel;
+    rsel = hit ? row : rsel;
+    wsel = hit ? w : wsel;
+    jsel = hit ? j : jsel;
+    j = hit ? -1 : (j < 0 ? j : j - c);
+  };
+  if (WPR == 1) {
+    const uint64_t real = tab->grid_real[0];
+    for (int row = 0; row < G; ++row) scan(row, 0, sg[row], real);
+  } else {
+    for (int row = 0; row < G; ++row)
+      for (int w = 0; w < WPR; ++w) scan(row, w, sg[row * WPR + w], tab->grid_real[w]);
   }
-  return 0;  // unreachable when j < count
+  const int pcol = wsel * 32 + (nth_even_bit(msel, jsel) >> 1);
+  row_o = msel ? rsel : 0;  // (no word selected: unreachable when j < count)
+  col_o = msel ? pcol - g.R : 0;
+  return msel != 0ull;
+}
+__device__ inline int img_nth_cell(const uint64_t* sg, const Geo& g, const Tables* tab, int j, int kind) {
+  int row, col;
+  img_nth_rc(sg, g, tab, j, kind, row, col);
+  return row * g.G + col;
 }
 
 // Obstacle clusters of _generate_map (plantos_env.py:341-354) on an empty image.
@@ -597,24 +632,23 @@ __device__ __forceinline__ Scal gen_map(const Geo& g, const Rules& rl, const Tab
     return s;
   }
   // random.sample(list(available), P): set-based selection, row-major list
+  // (picks: row << 8 | col -- G < 256 -- so that no lane divides by the runtime G)
   for (int i = 0; i < rl.P; ++i) {
-    int c;
+    int cx, cy;
     for (;;) {
-      c = img_nth_cell(sg, g, tab, (int)rng.below((uint32_t)nfree), 0);
-      if (img_code(sg, g, c / G, c % G + g.R) == EMPTY) break;  // else already selected
+      img_nth_rc(sg, g, tab, (int)rng.below((uint32_t)nfree), 0, cx, cy);
+      if (img_code(sg, g, cx, cy + g.R) == EMPTY) break;  // else already selected
     }
-    img_set(sg, g, c / G, c % G + g.R, HYD);
-    picks[i] = (uint16_t)c;
+    img_set(sg, g, cx, cy + g.R, HYD);
+    picks[i] = (uint16_t)((cx << 8) | cy);
   }
   // thirsty draws in sample order, plantos_env.py:367-369
   for (int i = 0; i < rl.P; ++i) {
     const int c = picks[i];
-    if (rng.random53() < rl.p_thirsty) img_set(sg, g, c / G, c % G + g.R, THIRSTY);
+    if (rng.random53() < rl.p_thirsty) img_set(sg, g, c >> 8, (c & 0xFF) + g.R, THIRSTY);
   }
   // rover: choice(list(available - plants)), plantos_env.py:370-372
-  const int rc = img_nth_cell(sg, g, tab, (int)rng.below((uint32_t)(nfree - rl.P)), 1);
-  s.x = rc / G;
-  s.y = rc % G;
+  img_nth_rc(sg, g, tab, (int)rng.below((uint32_t)(nfree - rl.P)), 1, s.x, s.y);
   return s;
 }
 
@@ -688,6 +722,17 @@ __device__ __forceinline__ Scal reset_env_scratch(const State& st, const Geo& g,
   uint64_t* gb = st.grid + e * g.gstride;
   for (int k = 0; k < g.G * g.WPR; ++k) gb[k] = sg[k];
   new_episode_visits(st, g, tab, e, s, keep);
+  return s;
+}
+
+// reset()'s map alone, generated in a scratch image (LDS): the caller writes the
+// grid rows, the visit rows (keep: CurriculumWrapper carries them) and the scalars.
+__device__ __forceinline__ Scal reset_env_image(const State& st, const Geo& g, const Rules& rl, const Tables* tab, int64_t e,
+                                       uint32_t episode, uint64_t* sg, bool& keep) {
+  keep = st.cur ? curriculum_on_reset(st.cur, e, rl) : false;
+  uint16_t* picks = reinterpret_cast<uint16_t*>(sg + g.G * g.WPR);
+  Scal s = gen_map(g, rl, tab, sg, picks, rl.env_off + (uint32_t)e, episode);
+  if (s.flags & F_NOROOM) atomicOr(st.err_bits, F_NOROOM);
   return s;
 }
 

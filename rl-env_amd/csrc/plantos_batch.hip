@@ -611,7 +611,19 @@ __device__ uint64_t g_dstamps[16384 * 8];
 #endif
 #ifdef PE_STAMPS_RESET
 #define PE_RSTAMP(k) PE_STAMP_RAW(k)
+// where the wave runs: HW_ID (wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]) | XCC_ID << 32
+#define PE_RSTAMP_HWID(k)                                                                   \
+  do {                                                                                      \
+    uint32_t _h, _x;                                                                        \
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(_h));                       \
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(_x));                      \
+    const int _w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);                     \
+    if ((threadIdx.x & 63) == 0 && _w < 16384) g_stamps[_w * 8 + (k)] = (uint64_t)_h | ((uint64_t)_x << 32); \
+  } while (0)
 #else
+#define PE_RSTAMP_HWID(k) \
+  do {                    \
+  } while (0)
 #define PE_RSTAMP(k) \
   do {               \
   } while (0)
@@ -679,6 +691,111 @@ __device__ __forceinline__ bool el_info_hit(int64_t e_info, int64_t e0, const fl
   // the block's one done env (the done mask in dist[70..71]) is the info wave's early env
   const uint64_t dmw = reinterpret_cast<const uint64_t*>(smem)[35];
   return e_info >= 0 && e_info == e0 + (__ffsll((unsigned long long)dmw) - 1);
+}
+
+// The second half of the lane-per-env reset of a block with many done envs (quad_done_path,
+// f32 tile), run by the commit wave with all lanes: each done lane's map lies as a grid
+// image in its own tile row (reset_env_image).  Lane l marches its env's rays from the image
+// (the results parked as bytes in `rays` [C][64]); then the wave as a whole copies the
+// images to the envs' grid blocks and writes the fresh visit slots with consecutive lanes on
+// consecutive words (one lane per env put every store of a wave instruction into a line of
+// its own); lane l stores its scalars and writes the fresh obs row over the dead image, so
+// that the tile store emits every row once.  Returns lane l's scalars.
+__device__ __forceinline__ Scal dense_reset_commit(const StepArgs& a, const Tables* ltab, float* rowsf, uint8_t* rays,
+                                                   const signed char* ldx, const signed char* ldy, int64_t e0, int lane,
+                                                   bool done, bool keep, Scal s) {
+  const Geo& g = a.g;
+  const State& st = a.st;
+  const int D = g.D, C = g.C, R = g.R, GW = g.G * g.WPR;
+  const uint64_t dm = __ballot(done);
+  const float* tdist = ltab->dist;
+  const float* tpos = ltab->pos;
+  const float* tvis = ltab->vis;
+  if (done) {  // as build_obs_fresh (plantos_env.py:260-292): distance | entity << 6
+    const uint64_t* sg = reinterpret_cast<const uint64_t*>(rowsf + lane * D + ((lane * D) & 1));
+    for (int i = 0; i < C; ++i) {
+      int dist = R, ent = EMPTY;
+      for (int r = 1; r <= R; ++r) {
+        const int cx = s.x + ldx[i * R + r - 1];
+        const int cy = s.y + ldy[i * R + r - 1];
+        const int code = (cx >= 0 && cx < g.G) ? img_code(sg, g, cx, cy + R) : OBST;  // :271-284
+        if (code != EMPTY) {
+          dist = r;
+          ent = code;
+          break;
+        }
+      }
+      rays[i * kQuadEnvs + lane] = (uint8_t)(dist | (ent << 6));
+    }
+  }
+  // the terminal info's reads of the old grid rows are consumed, and the commit's stores to
+  // them (the curriculum's watering / visit) have landed, before other lanes rewrite the rows
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  for (int u = lane; u < kQuadEnvs * GW; u += 64) {  // grid images -> grid blocks, 8-B words
+    const int l = u / GW, k = u - l * GW;
+    if ((dm >> l) & 1ull) {
+      const uint64_t* sl = reinterpret_cast<const uint64_t*>(rowsf + l * D + ((l * D) & 1));
+      st.grid[(e0 + l) * g.gstride + k] = sl[k];
+    }
+  }
+  // fresh visit slots (reset_visits: vis_pad everywhere, the rover's nibble 1) of the done
+  // envs that do not carry their counts; env l's new position / slot from lane l
+  const uint32_t pv = (uint32_t)s.x | ((uint32_t)s.y << 8) | ((s.episode & 1u) << 16) |
+                      ((s.flags & F_NOROOM) ? 1u << 17 : 0u) | ((done && !keep) ? 1u << 18 : 0u);
+  const int VS = (int)g.vslot, NWv = g.NW;
+  auto vword = [&](uint32_t q, int k) -> uint32_t {  // word k of env q's fresh slot
+    const int row = k / NWv, w = k - row * NWv;
+    const int bit = 4 * ((int)((q >> 8) & 0xFFu) + 2);
+    uint32_t v = ltab->vis_pad[w];
+    if (!(q & (1u << 17)) && row == (int)(q & 0xFFu) && w == (bit >> 5)) v = (v & ~(0xFu << (bit & 31))) | (1u << (bit & 31));
+    return v;
+  };
+  if ((VS & 3) == 0 && (reinterpret_cast<uintptr_t>(st.vis) & 15u) == 0) {  // 16-B units (vstride = 2 vslot)
+    const int U = VS >> 2;
+    for (int u = lane; u < kQuadEnvs * U; u += 64) {
+      const int l = u / U, k = u - l * U;
+      const uint32_t q = (uint32_t)__shfl((int)pv, l);
+      if (q & (1u << 18)) {
+        const uint4 v = make_uint4(vword(q, 4 * k), vword(q, 4 * k + 1), vword(q, 4 * k + 2), vword(q, 4 * k + 3));
+        *reinterpret_cast<uint4*>(st.vis + (e0 + l) * g.vstride + (int64_t)((q >> 16) & 1u) * g.vslot + 4 * k) = v;
+      }
+    }
+  } else {
+    for (int u = lane; u < kQuadEnvs * VS; u += 64) {
+      const int l = u / VS, k = u - l * VS;
+      const uint32_t q = (uint32_t)__shfl((int)pv, l);
+      if (q & (1u << 18)) st.vis[(e0 + l) * g.vstride + (int64_t)((q >> 16) & 1u) * g.vslot + k] = vword(q, k);
+    }
+  }
+  if (done) {
+    if (keep) new_episode_visits(st, g, ltab, e0 + lane, s, true);  // carried counts: lane by lane
+    st.ep_ret[e0 + lane] = 0.0;
+    st.scal[e0 + lane] = pack(s);
+  }
+  PE_RSTAMP(3);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every image is read out (LDS in order; the compiler: no reordering)
+  if (done) {  // as build_obs_fresh, into the env's tile row
+    float* out = rowsf + lane * D;
+    for (int i = 0; i < C; ++i) {
+      const int b = rays[i * kQuadEnvs + lane], ent = b >> 6;
+      out[5 * i] = tdist[b & 63];
+      out[5 * i + 1] = ent == 0 ? 1.0f : 0.0f;
+      out[5 * i + 2] = ent == 1 ? 1.0f : 0.0f;
+      out[5 * i + 3] = ent == 2 ? 1.0f : 0.0f;
+      out[5 * i + 4] = ent == 3 ? 1.0f : 0.0f;
+    }
+    out[5 * C] = tpos[s.x];
+    out[5 * C + 1] = tpos[s.y];
+    for (int lx = 0; lx < 5; ++lx)
+      for (int ly = 0; ly < 5; ++ly) {
+        const int gx = s.x + lx - 2, gy = s.y + ly - 2;
+        const bool in = gx >= 0 && gx < g.G && gy >= 0 && gy < g.G;  // :307-311
+        const bool rover = lx == 2 && ly == 2 && !(s.flags & F_NOROOM);
+        out[5 * C + 2 + 5 * lx + ly] = !in ? tvis[10] : (rover ? tvis[1] : tvis[0]);
+      }
+  }
+  PE_RSTAMP(4);
+  return s;
 }
 
 // BT: the obs tile holds byte codes (ctab: the LDS code table), see pe_step_quad.
@@ -1089,8 +1206,8 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
   // Many done envs (a synchronized batch truncating together): one lane per env.
   // The done env's own obs-tile row is free once its terminal obs is copied out:
   // the new map is generated there when it can hold the grid image (LDS latency
-  // for the rejection-sampling scans; the fresh obs row goes straight to HBM
-  // after the tile store, quad_done_obs)
+  // for the rejection-sampling scans); the fresh obs row then replaces the image
+  // and goes out with the tile (dense_reset_commit)
   // (BT: the tile row holds D bytes, never the image; the fresh obs of that case is
   // built from the env's grid in HBM after the tile store, quad_done_obs)
   const bool scratch_ok = !BT && reset_scratch_bytes(g.G, g.WPR, rl.P) <= 4 * g.D;
@@ -1100,38 +1217,73 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
   const signed char* lldx = reinterpret_cast<const signed char*>(lrow);
   const signed char* lldy = lldx + C * R;
   PE_RSTAMP(0);
+  PE_RSTAMP_HWID(6);
   load_tables_cold(smem, st.tab);
   for (int k = threadIdx.x; k < C * R; k += blockDim.x) {
     reinterpret_cast<signed char*>(lrow)[k] = st.ldx[k];
     reinterpret_cast<signed char*>(lrow)[C * R + k] = st.ldy[k];
   }
   __syncthreads();
-  if (done) {
+  if constexpr (!BT) {
+    // f32 tile: the terminal obs rows go out by the whole block, lanes across a row,
+    // before the generator reuses the rows (one lane per env wrote D stores at a
+    // D-float lane stride: every store of a wave instruction in a line of its own)
     if (a.tobs) {
-      float* t = a.tobs + e * g.D;
-      for (int k = 0; k < g.D; ++k) t[k] = tval(row, k);
+      const uint64_t dml = reinterpret_cast<const uint64_t*>(smem)[35];
+      uint64_t dm = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)dml) |
+                    ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(dml >> 32)) << 32);
+      if (dm == ~0ull) {  // every env of a full block: the tile as it is
+        store_tile(reinterpret_cast<const float*>(rows), a.tobs + e0 * g.D, kQuadEnvs, g.D, g.D);
+      } else {  // done rows only, the k-th to wave k % NW
+        const int NWv = blockDim.x >> 6;
+        for (int k = 0; dm; ++k) {
+          const int l = __ffsll((unsigned long long)dm) - 1;
+          dm &= dm - 1;
+          if (k % NWv != wv) continue;
+          const float* r = reinterpret_cast<const float*>(rows) + l * g.D;
+          float* t = a.tobs + (e0 + l) * g.D;
+          for (int k2 = lane; k2 < g.D; k2 += 64) t[k2] = r[k2];
+        }
+      }
+      __syncthreads();  // the rows are read out
+    }
+  }
+  bool keep = false;
+  if (done) {
+    if constexpr (BT) {
+      if (a.tobs) {
+        float* t = a.tobs + e * g.D;
+        for (int k = 0; k < g.D; ++k) t[k] = tval(row, k);
+      }
     }
     PE_RSTAMP(1);
     if (a.tinfo) write_info(a.st, a.g, ltab, e, s, a.tinfo + e * PE_NINFO, wfix);
     PE_RSTAMP(2);
     if (!a.autoreset) {
     } else if (scratch_ok) {
-      s = reset_env_scratch(st, g, rl, ltab, e, s.episode, sg);
-      PE_RSTAMP(3);
+      // the map into the env's tile row; grid, visits, scalars and the fresh obs row
+      // follow from the commit wave as a whole (dense_reset_commit)
+      s = reset_env_image(st, g, rl, ltab, e, s.episode, sg, keep);
     } else {
       s = reset_env(st, g, rl, ltab, e, s.episode);
       if constexpr (!BT) build_obs_fresh(a, st.grid + e * g.gstride, s, row, tdist, tpos, tvis, lldx, lldy);
-    }
-    if (a.autoreset) {
       st.ep_ret[e] = 0.0;
       st.scal[e] = pack(s);
+    }
+  }
+  if constexpr (!BT) {
+    if (a.autoreset && scratch_ok && wv == CW) {
+      // the marched rays wait as bytes [C][64] behind the LIDAR offsets in the window region
+      uint8_t* rays = reinterpret_cast<uint8_t*>(lrow) + ((2 * C * R + 15) & ~15);
+      s = dense_reset_commit(a, ltab, reinterpret_cast<float*>(rows), rays, lldx, lldy, e0, lane, done, keep, s);
     }
   }
   __syncthreads();
   return pack(s);
 }
 
-// The lane-per-env path's fresh obs, after the tile store (see quad_done_path).
+// The lane-per-env path's fresh obs, after the tile store (see quad_done_path): the byte-tile
+// kernels' (the f32 kernels write the fresh row into the tile, dense_reset_commit).
 template <int NW, bool BT = false>
 __device__ __forceinline__ void quad_done_obs(const void* ka, int tile_off, int lane, int64_t e, bool done, uint4 sp) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -2024,14 +2176,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
         store_tile(rows, a.obs + e0 * g.D, (int)valid, g.D, g.D, (int)threadIdx.x, 64 * (NW - 1));
     }
   }
-  if (any_done && a.autoreset && !quad_coop(a, ndone) && (BT || reset_scratch_bytes(g.G, g.WPR, rl.P) <= 4 * g.D)) {
-    // the tile store above wrote stale values (scratch bytes / the terminal codes)
-    // into the done rows: drain it, then overwrite those rows with the fresh obs built
-    // from the grid image (LDS scratch, or BT: the env's rows in HBM)
+  if constexpr (BT) {
+    if (any_done && a.autoreset && !quad_coop(a, ndone)) {
+      // the tile store above wrote stale values (the terminal codes) into the done rows:
+      // drain it, then overwrite those rows with the fresh obs built from the env's rows
+      // in HBM (the f32 tile's lane path left its fresh rows in the tile: dense_reset_commit)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      quad_done_obs<NW, BT>(kernargs(), tile_off, lane, e, done, pack(s));
+    }
+  }
+#ifdef PE_STAMPS_RESET
+  if (!BT && any_done && !quad_coop(a, ndone)) {  // R5: the block's tile (fresh rows included) has landed
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    quad_done_obs<NW, BT>(kernargs(), tile_off, lane, e, done, pack(s));
+    PE_RSTAMP(5);
   }
+#endif
   PE_STAMP(6);
 #ifdef PE_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

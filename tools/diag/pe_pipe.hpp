@@ -227,13 +227,8 @@ __global__ __launch_bounds__(256, WPC) void pe_step_pipe(StepArgs a0) {
     } else {
       __builtin_amdgcn_s_waitcnt(kVmcnt0);
     }
-    if (any_done && a.autoreset && !quad_coop(a, ndone) && reset_scratch_bytes(a.g.G, a.g.WPR, a.rl.P) <= 4 * a.g.D) {
-      // the lane-per-env reset's fresh obs over the stale tile rows (see pe_step_quad)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      quad_done_obs<NW, false>(kernargs(), tile_off, lane, e, done, pack(s));
-      __syncthreads();  // its reads of the window region (LIDAR offsets) before block bn's rows
-    }
+    // (the lane-per-env reset leaves its fresh obs rows in the tile: quad_done_path's
+    // dense branch; its last barrier is behind its reads of the window region)
     if (!more) break;
     pipe_window<R, LT, JV>(a, bn, le, sub, nxt, qv, lrow, lvis);
     cur = nxt;
