@@ -347,10 +347,12 @@ __device__ __forceinline__ int visit_exact(const State& st, const Geo& g, int64_
 // overflow slot is set at the 15th visit and bumped in memory after that.  The
 // headline sector kernel (pe_step_quad<C16,R6,1word>, 64 envs) defers that write as a
 // vpend entry (vx_pending), stores it, and applies the previous step's early in the next
-// launch (vx_apply; the same lane, program order): a write to vx issued at the commit --
-// one per ~100 env-steps, each to a cold line of a 105 MB array at 65536 envs -- held
-// the launch's end (profiles/r4p/, r4q/).  Every other step kernel writes at once
-// (visit_bump_exact): their handles never hold a pending word.
+// launch (vx_apply; the same lane, program order): a write to vx issued at the commit,
+// each to a cold line of a 105 MB array at 65536 envs, held the launch's end
+// (profiles/r4p/, r4q/).  Such a write is no rarity: bench.py's 64-row action stream has
+// every env pacing a few cells, and a third of its env-steps move into a cell already at
+// >= 14 (tools/visit_overflow_rate.py; DESIGN.md §8 "visit counts past 15").  Every other
+// step kernel writes at once (visit_bump_exact): their handles never hold a pending word.
 enum : uint32_t { VP_SET15 = 1u << 31, VP_INC = 1u << 30, VP_CELL = VP_INC - 1u };
 __device__ __forceinline__ uint32_t vx_pending(int cell, uint32_t n) {
   return n == 14u ? (VP_SET15 | (uint32_t)cell) : (n == 15u ? (VP_INC | (uint32_t)cell) : 0u);

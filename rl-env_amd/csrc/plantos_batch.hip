@@ -1506,6 +1506,10 @@ __device__ __forceinline__ void quad_compute(const StepArgs& a, const uint64_t* 
           // nibbles): one byte store, no read of the word from memory
           const int p = m.ny + 2, b = p >> 1;
           const uint32_t wnew = (lvis[(3 + m.dxm) * LS + lane] & ~(0xFu << (4 * (p - m.ybv)))) | (nib << (4 * (p - m.ybv)));
+          // (not at a saturated nibble: the store would rewrite the byte memory already holds.
+          // The flagship's action stream moves into a cell at 15 in three of ten env-steps,
+          // tools/visit_overflow_rate.py; the A/B: profiles/visit_overflow_ab.json)
+          if (n < 15u) {
 #if defined(PE_PROBE_VISIDLE)  // (timing / traffic probe, wrong results: the byte into the idle slot)
           st_wt(reinterpret_cast<uint8_t*>(vis_env(st, g, e, s.episode ^ 1u) + (int64_t)m.nx * g.NW) + b,
                 (uint8_t)(wnew >> (4 * (2 * b - m.ybv))));
@@ -1516,10 +1520,15 @@ __device__ __forceinline__ void quad_compute(const StepArgs& a, const uint64_t* 
           st_wt(reinterpret_cast<uint8_t*>(vis_env(st, g, e, s.episode) + (int64_t)m.nx * g.NW) + b,
                 (uint8_t)(wnew >> (4 * (2 * b - m.ybv))));
 #endif
+          }
+#if defined(PE_PROBE_NOVX)  // (timing probe, counts past 15 wrong: no overflow bookkeeping at all)
+          if constexpr (!DV) visit_bump_exact(st, g, e, m.cell_n, n);
+#else
           if constexpr (DV)
             np = vx_pending(m.cell_n, n);
           else
             visit_bump_exact(st, g, e, m.cell_n, n);
+#endif
           if (s.flags & F_EXPL_BITMAP) {
             uint32_t* ep_o = st.expl + e * g.estride + (m.cell_o >> 5);
             uint32_t* ep_n = st.expl + e * g.estride + (m.cell_n >> 5);
@@ -1642,7 +1651,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // (round 5: the byte-coded twin of the headline kernel too -- config 5's codes step, A/B
   // PE_BT_DV=0)
   constexpr bool DV = C == 16 && R == 6 && ONEWORD && NW == 4 && (PE_BT_DV || !BT) && EPB == kQuadEnvs;
+#if defined(PE_PROBE_NOVX)  // (timing probe: the DV kernels without their vpend load, apply and store)
+  const uint32_t vp0 = 0u;
+#else
   const uint32_t vp0 = DV ? st.vpend[wv == CW || wv == 0 ? ec : 0] : 0u;  // (wave 0 applies, CW stores)
+#endif
   // (Tried: the loader env's position by a bpermute from lane le of the wave instead of
   // this load -- 64x64 24.5 -> 25.2 us, 25x25 desync +0.4 us, the headline unchanged;
   // profiles/r3m_ab_*.jsonl.)
