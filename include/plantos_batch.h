@@ -305,6 +305,83 @@ int pe_render_tables(const pe_config* c, int32_t cell_size, int32_t* ray_ends, u
 int pe_render(pe_handle* h, int32_t k, const int32_t* env_index_or_null, int32_t cell_size, uint8_t* out,
               int64_t frame_stride, int64_t row_stride, void* stream);
 
+/* Policy inference: a batched SB3-shaped MLP from the obs of `h`'s envs to their next
+ * actions (A2C("MlpPolicy", net_arch=[256,256]) A2C_training.py:229-247; DQN("MlpPolicy",
+ * net_arch=[512,512,256]) trainingCode.py:226-246; model.predict(obs, deterministic=True)
+ * in the evaluation loops).  Learners stay out of scope.
+ *
+ * Definition (the host twin pe_policy_forward_host executes it literally; the kernel gives
+ * the same bits):
+ *  - A policy is 1 or 2 towers over the same obs row x[0..D), D = 5C + 27.  A tower is
+ *    1..3 hidden Linear layers (widths multiples of 32 in 32..512) and a head Linear;
+ *    weights in torch's nn.Linear layout (weight[out][in] row-major, bias[out]), f32.
+ *    Tower 0's head has A outputs, 2 <= A <= 8 (action logits or Q-values); tower 1's
+ *    head, if present, has 1 output (the value).  That is SB3 2.2.1's ActorCriticPolicy
+ *    with separate pi / vf nets (Tanh) and DQN's QNetwork (one tower, ReLU); anything else
+ *    is PE_ERR_ARG.
+ *  - Pre-activation z_j: ONE f32 fma chain, acc = b_j; for k = 0..K-1 ascending:
+ *    acc = fmaf(w[j][k], x[k], acc).  No split-K, no other association (zero padding after
+ *    k = K-1 cannot change a value and is allowed).
+ *  - One activation for all hidden layers, none on the heads: PE_ACT_RELU is
+ *    z > 0 ? z : 0; PE_ACT_TANH is pe_tanhf, a function this project defines
+ *    (rl-env_amd/csrc/pe_policy_math.hpp) from fmaf, f32 add / mul / div and bit
+ *    operations only, identical on host and device (worst error against tanh: DESIGN.md
+ *    section 4).
+ *  - PE_POLICY_ARGMAX: the first index of the maximum of tower 0's head (torch.argmax;
+ *    deterministic=True of the A2C policy, DQN's greedy action).
+ *  - PE_POLICY_SAMPLE: u = (philox4x32-10(ctr = (t, env_id_offset + e, 0, 0x594C4F50),
+ *    key = seed).x >> 8) * 2^-24 (pe_synth_actions' counter layout, another domain word);
+ *    p_a = pe_expf(l_a - max l) (the project's exp, same header); cumulative sums in action
+ *    order in f32, S the last; the action is the first a with u * S < cum_a, else A - 1.
+ *    The sampler is this project's own: SB3 draws from torch's generator, which is not
+ *    reproduced.
+ *
+ * pe_policy_tower carries a tower's shape and, for load / the host twin, its tensors:
+ * weight[l] / bias[l] of Linear l (hidden layers in order, then the head). */
+enum pe_activation { PE_ACT_TANH = 0, PE_ACT_RELU = 1 };
+enum pe_policy_mode { PE_POLICY_ARGMAX = 0, PE_POLICY_SAMPLE = 1 };
+typedef struct pe_policy_tower {
+    int32_t n_hidden;          /* 1..3 */
+    int32_t hidden[3];         /* widths of the hidden layers */
+    int32_t n_out;             /* head outputs: A (tower 0) or 1 (tower 1) */
+    int32_t reserved[3];
+    const float* weight[4];    /* n_hidden + 1 tensors f32[out][in] (pe_policy_create ignores them) */
+    const float* bias[4];      /* n_hidden + 1 tensors f32[out] */
+} pe_policy_tower;
+typedef struct pe_policy pe_policy;
+
+/* Shapes only: allocates the packed device weights (zeroed) for `h`'s obs length and
+ * chooses the kernel's env tile.  env_tile: envs per workgroup, 32 or 64, or 0 for the
+ * library's choice (speed only: every tile gives the same results); PE_ERR_ARG if the
+ * tile's activations do not fit the 160 KiB of LDS (512-wide layers need 32).
+ * The policy must be destroyed before `h`. */
+int pe_policy_create(pe_handle* h, int32_t n_towers, const pe_policy_tower* shapes, int32_t activation,
+                     int32_t env_tile, pe_policy** out);
+int pe_policy_destroy(pe_policy* p);
+/* Repack the caller's DEVICE tensors (towers[i].weight / bias) into the policy's own
+ * layout: one kernel, asynchronous on `stream`, no allocation (a learner calls it after
+ * every optimizer step).  The shapes are the ones given to pe_policy_create. */
+int pe_policy_load(pe_policy* p, const pe_policy_tower* towers, void* stream);
+/* One forward of all n envs of the handle: obs u8[n, D] byte codes as pe_step_codes
+ * writes them (obs_is_codes = 1; handles created with obs_codes; decoded through
+ * pe_obs_code_table's table) or f32[n, D] as pe_step / pe_reset write them.  actions
+ * i32[n]; head0 f32[n, A] and head1 f32[n] may be NULL (head1 must be NULL for a
+ * one-tower policy).  seed / t are read in PE_POLICY_SAMPLE mode only.  One kernel, no host
+ * sync, no allocation: graph-capturable. */
+int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32_t mode, uint64_t seed,
+                      uint32_t t, int32_t* actions, float* head0_or_null, float* head1_or_null, void* stream);
+/* The host twin: the definition above in plain C++ on HOST arrays (no handle, no device).
+ * obs f32[n, D]; towers with host tensors; outputs as pe_policy_forward (head0 / head1
+ * may be NULL). */
+int pe_policy_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe_policy_tower* towers,
+                           int32_t activation, const float* obs, int32_t mode, uint64_t seed,
+                           uint32_t env_id_offset, uint32_t t, int32_t* actions, float* head0_or_null,
+                           float* head1_or_null);
+/* pe_tanhf / pe_expf of n host floats (tests and the accuracy tool measure them). */
+int pe_policy_math_host(int32_t which, int32_t n, const float* x, float* y);
+/* Envs per workgroup of the forward kernel (introspection). */
+int32_t pe_policy_env_tile(const pe_policy* p);
+
 /* Introspection for tests / benchmarks. */
 int32_t pe_num_envs(const pe_handle* h);
 int32_t pe_kernel_variant(const pe_handle* h);  /* 0 generic, >0 specialized geometry */

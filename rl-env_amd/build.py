@@ -4,7 +4,7 @@
   python rl-env_amd/build.py            # build if sources changed
   python rl-env_amd/build.py --force
 
-The four translation units are compiled in parallel (hipcc -c) and linked into
+The translation units are compiled in parallel (hipcc -c) and linked into
 one shared library; the result is byte-identical from run to run (bench.py keys
 its committed PMC profiles by the library's hash).
 """
@@ -21,9 +21,12 @@ SRC = os.path.join(HERE, "csrc", "plantos_batch.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "pe_pystream.cpp")
 SRC_MCTS = os.path.join(HERE, "csrc", "pe_mcts.hip")
 SRC_RENDER = os.path.join(HERE, "csrc", "pe_render.hip")
-SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST]
+SRC_POLICY = os.path.join(HERE, "csrc", "pe_policy.hip")
+SRC_POLICY_HOST = os.path.join(HERE, "csrc", "pe_policy_host.cpp")
+SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in
-                  ("pe_device.hpp", "pe_fast.hpp", "pe_quad.hpp", "pe_coop.hpp", "pe_handle.hpp", "pe_far.hpp")] + [
+                  ("pe_device.hpp", "pe_fast.hpp", "pe_quad.hpp", "pe_coop.hpp", "pe_handle.hpp", "pe_far.hpp",
+                   "pe_policy_math.hpp")] + [
     os.path.join(REPO, "include", "plantos_batch.h"), os.path.join(HERE, "tools_gen_lidar.py")]
 OUT = os.path.join(HERE, "plantos_amd", "libplantos_hip.so")
 OBJ_DIR = os.path.join(REPO, "build", "obj")

@@ -1,0 +1,135 @@
+// pe_policy_host.cpp -- the host twin of pe_policy_forward (include/plantos_batch.h,
+// "Policy inference"): the definition executed literally, one fmaf chain per
+// pre-activation in ascending k, pe_tanhf / pe_expf / the sampler from the header the
+// kernel includes too.  Plain C++: no handle, no device.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/plantos_batch.h"
+#include "pe_policy_math.hpp"
+
+extern "C" int pe_internal_set_error(int code, const char* msg);
+
+// Shape rules of a policy (shared with pe_policy.hip); with_ptrs: the tensors must be there.
+extern "C" int pe_internal_policy_check(int32_t n_towers, const pe_policy_tower* tw, int32_t activation,
+                                        int with_ptrs) {
+  auto fail = [](const std::string& m) { return pe_internal_set_error(PE_ERR_ARG, m.c_str()); };
+  if (!tw) return fail("null towers");
+  if (n_towers < 1 || n_towers > 2) return fail("a policy has 1 or 2 towers");
+  if (activation != PE_ACT_TANH && activation != PE_ACT_RELU) return fail("activation must be PE_ACT_TANH or PE_ACT_RELU");
+  for (int i = 0; i < n_towers; ++i) {
+    const pe_policy_tower& t = tw[i];
+    if (t.n_hidden < 1 || t.n_hidden > 3) return fail("a tower has 1..3 hidden layers");
+    for (int l = 0; l < t.n_hidden; ++l)
+      if (t.hidden[l] < 32 || t.hidden[l] > 512 || (t.hidden[l] & 31))
+        return fail("hidden widths must be multiples of 32 in 32..512");
+    if (i == 0 && (t.n_out < 2 || t.n_out > 8)) return fail("tower 0's head must have 2..8 outputs");
+    if (i == 1 && t.n_out != 1) return fail("tower 1's head must have 1 output");
+    if (with_ptrs)
+      for (int l = 0; l <= t.n_hidden; ++l)
+        if (!t.weight[l] || !t.bias[l]) return fail("null weight or bias tensor");
+  }
+  return PE_OK;
+}
+
+namespace {
+using namespace pe_pol;
+
+// One pre-activation: the fmaf chain of the definition.  HW: the caller is compiled for the
+// CPU's fused multiply-add, which gives the bits of libm's fmaf (both round once).
+template <bool HW>
+__attribute__((always_inline)) inline float chain(const float* w, const float* x, int K, float acc) {
+  for (int k = 0; k < K; ++k) acc = HW ? __builtin_fmaf(w[k], x[k], acc) : std::fmaf(w[k], x[k], acc);
+  return acc;
+}
+
+// One tower on one obs row: out[0..n_out).
+template <bool HW>
+__attribute__((always_inline)) inline void tower_body(const pe_policy_tower& t, int D, int activation, const float* x,
+                                                      float* out) {
+  float a[512], b[512];
+  const float* in = x;
+  int K = D;
+  float* cur = a;
+  for (int l = 0; l <= t.n_hidden; ++l) {
+    const bool head = l == t.n_hidden;
+    const int N = head ? t.n_out : t.hidden[l];
+    float* dst = head ? out : cur;
+    int j = 0;
+    for (; j + 4 <= N; j += 4) {  // four neurons' chains side by side (each still one chain in k order)
+      const float* w = t.weight[l] + (size_t)j * K;
+      float acc[4] = {t.bias[l][j], t.bias[l][j + 1], t.bias[l][j + 2], t.bias[l][j + 3]};
+      for (int k = 0; k < K; ++k)
+        for (int q = 0; q < 4; ++q)
+          acc[q] = HW ? __builtin_fmaf(w[(size_t)q * K + k], in[k], acc[q]) : std::fmaf(w[(size_t)q * K + k], in[k], acc[q]);
+      for (int q = 0; q < 4; ++q)
+        dst[j + q] = head ? acc[q] : (activation == PE_ACT_TANH ? pe_tanhf(acc[q]) : pe_relu(acc[q]));
+    }
+    for (; j < N; ++j) {
+      const float acc = chain<HW>(t.weight[l] + (size_t)j * K, in, K, t.bias[l][j]);
+      dst[j] = head ? acc : (activation == PE_ACT_TANH ? pe_tanhf(acc) : pe_relu(acc));
+    }
+    in = dst;
+    K = N;
+    cur = cur == a ? b : a;
+  }
+}
+
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+__attribute__((target("fma"))) void tower_forward_hw(const pe_policy_tower& t, int D, int activation, const float* x,
+                                                     float* out) {
+  tower_body<true>(t, D, activation, x, out);
+}
+bool have_hw_fma() { return __builtin_cpu_supports("fma"); }
+#else
+void tower_forward_hw(const pe_policy_tower& t, int D, int activation, const float* x, float* out) {
+  tower_body<false>(t, D, activation, x, out);
+}
+bool have_hw_fma() { return false; }
+#endif
+
+void tower_forward(const pe_policy_tower& t, int D, int activation, const float* x, float* out) {
+  static const bool hw = have_hw_fma();
+  if (hw)
+    tower_forward_hw(t, D, activation, x, out);
+  else
+    tower_body<false>(t, D, activation, x, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pe_policy_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe_policy_tower* towers,
+                           int32_t activation, const float* obs, int32_t mode, uint64_t seed,
+                           uint32_t env_id_offset, uint32_t t, int32_t* actions, float* head0, float* head1) {
+  if (const int rc = pe_internal_policy_check(n_towers, towers, activation, 1)) return rc;
+  if (n < 0 || D < 1 || !obs || !actions) return pe_internal_set_error(PE_ERR_ARG, "bad n / D or null obs / actions");
+  if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
+    return pe_internal_set_error(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
+  if (head1 && n_towers < 2) return pe_internal_set_error(PE_ERR_ARG, "head1 needs a second tower");
+  const int A = towers[0].n_out;
+  for (int e = 0; e < n; ++e) {
+    const float* x = obs + (size_t)e * D;
+    float l[8], v;
+    tower_forward(towers[0], D, activation, x, l);
+    if (n_towers == 2) {
+      tower_forward(towers[1], D, activation, x, &v);
+      if (head1) head1[e] = v;
+    }
+    if (head0) std::memcpy(head0 + (size_t)e * A, l, sizeof(float) * A);
+    actions[e] = mode == PE_POLICY_ARGMAX ? policy_argmax(l, A)
+                                          : policy_sample(l, A, policy_uniform(seed, env_id_offset + (uint32_t)e, t));
+  }
+  return PE_OK;
+}
+
+int pe_policy_math_host(int32_t which, int32_t n, const float* x, float* y) {
+  if (n < 0 || (n > 0 && (!x || !y)) || which < 0 || which > 1)
+    return pe_internal_set_error(PE_ERR_ARG, "which must be 0 (pe_tanhf) or 1 (pe_expf); null argument");
+  for (int i = 0; i < n; ++i) y[i] = which == 0 ? pe_tanhf(x[i]) : pe_expf(x[i]);
+  return PE_OK;
+}
+
+}  // extern "C"

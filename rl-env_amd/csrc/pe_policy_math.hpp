@@ -1,0 +1,146 @@
+// pe_policy_math.hpp -- the scalar functions of the policy definition (include/plantos_batch.h,
+// "Policy inference"), shared by the host twin (pe_policy_host.cpp) and the kernel
+// (pe_policy.hip), so both execute the same operations in the same order.
+//
+// Everything here is built from operations that are correctly rounded and identical on the
+// host and on gfx950: fmaf, f32 add / sub / mul / div, comparisons, integer and bit
+// operations.  No libm / ocml transcendental, no a*b+c left to the compiler (every
+// multiply-add is an explicit fmaf and contraction is switched off inside each function),
+// no fast-math.  Subnormals are kept on both sides.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <cmath>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PE_HD __host__ __device__ inline
+#else
+#define PE_HD inline
+#endif
+
+namespace pe_pol {
+
+constexpr uint32_t kDomainPolicy = 0x594C4F50u;  // Philox counter domain word of the action sampler
+
+PE_HD float bits_to_float(uint32_t u) {
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+PE_HD uint32_t float_to_bits(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return u;
+}
+
+// exp(x) in f32 for x clamped to [-87, 88] (NaN passes through): n = round(x log2 e) by the
+// 1.5 * 2^23 trick, r = x - n ln2 in two fmaf steps (ln2 split hi + lo), a degree-7 Taylor
+// polynomial in fmaf, then one multiply by 2^n built from its bits.
+PE_HD float pe_expf(float x) {
+#pragma clang fp contract(off)
+  if (x != x) return x;
+  x = x < -87.0f ? -87.0f : (x > 88.0f ? 88.0f : x);
+  const float magic = 12582912.0f;  // 1.5 * 2^23
+  const float t = fmaf(x, 1.44269504088896341f, magic);
+  const float nf = t - magic;
+  float r = fmaf(nf, -0.693145751953125f, x);      // ln2 hi
+  r = fmaf(nf, -1.42860682030941723e-06f, r);      // ln2 lo
+  float p = 1.98412698412698413e-04f;              // 1/5040
+  p = fmaf(p, r, 1.38888888888888894e-03f);        // 1/720
+  p = fmaf(p, r, 8.33333333333333322e-03f);        // 1/120
+  p = fmaf(p, r, 4.16666666666666644e-02f);        // 1/24
+  p = fmaf(p, r, 1.66666666666666657e-01f);        // 1/6
+  p = fmaf(p, r, 0.5f);
+  p = fmaf(p, r, 1.0f);
+  p = fmaf(p, r, 1.0f);
+  const int32_t n = (int32_t)nf;                   // -126 .. 127: 2^n is a normal float
+  return p * bits_to_float((uint32_t)(n + 127) << 23);
+}
+
+// tanh(x) in f32.  |x| < 0.55: x + x^3 P(x^2), P a degree-5 polynomial (a weighted minimax
+// fit of (tanh(x)/x - 1)/x^2 on x^2 in [0, 0.3025]) in fmaf;
+// 0.55 <= |x| <= 9.1: 1 - 2 / (exp(2|x|) + 1); above: 1 (tanh rounds to 1 from 9.02 on).
+// The sign is copied from x's bit; NaN passes through; tanh(+-0) = +-0.
+PE_HD float pe_tanhf(float x) {
+#pragma clang fp contract(off)
+  if (x != x) return x;
+  const uint32_t sign = float_to_bits(x) & 0x80000000u;
+  const float ax = bits_to_float(float_to_bits(x) & 0x7FFFFFFFu);
+  float y;
+  if (ax < 0.55f) {
+    const float s = ax * ax;
+    float p = 0.002398997312411666f;
+    p = fmaf(p, s, -0.008416792377829552f);
+    p = fmaf(p, s, 0.021783767268061638f);
+    p = fmaf(p, s, -0.053959790617227554f);
+    p = fmaf(p, s, 0.13333295285701752f);
+    p = fmaf(p, s, -0.3333333134651184f);
+    const float xs = ax * s;
+    y = fmaf(xs, p, ax);
+  } else if (ax <= 9.1f) {
+    const float e = pe_expf(ax + ax);
+    const float d = e + 1.0f;
+    const float q = 2.0f / d;
+    y = 1.0f - q;
+  } else {
+    y = 1.0f;
+  }
+  return bits_to_float(float_to_bits(y) | sign);
+}
+
+PE_HD float pe_relu(float z) { return z > 0.0f ? z : 0.0f; }
+
+// Philox4x32-10, the counter / key layout of the env's generator (pe_device.hpp,
+// oracle/plantos_oracle.c); written with 64-bit products so host and device share it.
+struct U4 {
+  uint32_t x, y, z, w;
+};
+PE_HD U4 philox4x32(U4 c, uint32_t k0, uint32_t k1) {
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
+    const U4 o = {(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
+    c = o;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+
+// u in [0, 1) of env `env_id` (global id) at step t: 24 bits of one Philox block.
+PE_HD float policy_uniform(uint64_t seed, uint32_t env_id, uint32_t t) {
+  const U4 c = {t, env_id, 0u, kDomainPolicy};
+  const U4 o = philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (float)(o.x >> 8) * 5.9604644775390625e-08f;  // 2^-24: exact
+}
+
+// First index of the maximum (torch.argmax; a NaN never wins over an earlier entry).
+PE_HD int policy_argmax(const float* l, int A) {
+  int best = 0;
+  for (int a = 1; a < A; ++a)
+    if (l[a] > l[best]) best = a;
+  return best;
+}
+
+// Categorical sample: p_a = pe_expf(l_a - max l), cumulative sums in action order in f32,
+// the first a with u * S < cum_a, else A - 1.
+PE_HD int policy_sample(const float* l, int A, float u) {
+#pragma clang fp contract(off)
+  float m = l[0];
+  for (int a = 1; a < A; ++a) m = l[a] > m ? l[a] : m;
+  float p[8];
+  float S = 0.0f;
+  for (int a = 0; a < A; ++a) {
+    p[a] = pe_expf(l[a] - m);
+    S = S + p[a];
+  }
+  const float us = u * S;
+  float cum = 0.0f;
+  for (int a = 0; a < A; ++a) {
+    cum = cum + p[a];
+    if (us < cum) return a;
+  }
+  return A - 1;
+}
+
+}  // namespace pe_pol

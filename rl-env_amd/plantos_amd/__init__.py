@@ -4,8 +4,10 @@ Public surface:
   PlantOSBatch      N envs in HBM, device tensors in/out (C-ABI: include/plantos_batch.h)
   PlantOSVecEnv     Stable-Baselines3 VecEnv drop-in for DummyVecEnv (A2C_training.py:216-218)
   PlantOSVectorEnv  gymnasium-0.29 VectorEnv convention over the same batch
+  Policy            batched MLP policy inference on the device: obs (codes or f32) -> actions
 """
 from .batch import PlantOSBatch  # noqa: F401
+from .policy import Policy  # noqa: F401
 from .vec_env import PlantOSVecEnv, PlantOSVectorEnv  # noqa: F401
 
-__all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv"]
+__all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy"]

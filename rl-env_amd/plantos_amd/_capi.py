@@ -42,7 +42,11 @@ EXPORTS = [
     "pe_mcts_create", "pe_mcts_destroy", "pe_mcts_seed", "pe_mcts_set_rng", "pe_mcts_get_rng", "pe_mcts_search",
     "pe_step_codes", "pe_obs_code_table", "pe_expand_obs_codes",
     "pe_render_tables", "pe_render",
+    "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward", "pe_policy_forward_host",
+    "pe_policy_math_host", "pe_policy_env_tile",
 ]
+PE_ACT_TANH, PE_ACT_RELU = 0, 1
+PE_POLICY_ARGMAX, PE_POLICY_SAMPLE = 0, 1
 
 
 class PEConfig(ctypes.Structure):
@@ -56,6 +60,13 @@ class PEConfig(ctypes.Structure):
         ("env_id_offset", ctypes.c_uint32), ("map_generation_algo", ctypes.c_int32),
         ("coop_max_done", ctypes.c_int32), ("prefetch_every", ctypes.c_int32), ("obs_codes", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
+class PEPolicyTower(ctypes.Structure):
+    _fields_ = [
+        ("n_hidden", ctypes.c_int32), ("hidden", ctypes.c_int32 * 3), ("n_out", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 3), ("weight", ctypes.c_void_p * 4), ("bias", ctypes.c_void_p * 4),
     ]
 
 
@@ -127,7 +138,18 @@ def lib():
     if hasattr(L, "pe_render"):  # (an older library loaded for a same-box A/B lacks them)
         L.pe_render_tables.argtypes = [CP, I32, P, P]
         L.pe_render.argtypes = [P, I32, P, I32, P, ctypes.c_int64, ctypes.c_int64, P]
-    for name in ("pe_create", "pe_destroy", "pe_seed", "pe_reset", "pe_step", "pe_get_info", "pe_get_state",
+    if hasattr(L, "pe_policy_create"):  # (an older library loaded for a same-box A/B lacks them)
+        TP = ctypes.POINTER(PEPolicyTower)
+        L.pe_policy_create.argtypes = [P, I32, TP, I32, I32, ctypes.POINTER(P)]
+        L.pe_policy_destroy.argtypes = [P]
+        L.pe_policy_load.argtypes = [P, TP, P]
+        L.pe_policy_forward.argtypes = [P, P, I32, I32, U64, U32, P, P, P, P]
+        L.pe_policy_forward_host.argtypes = [I32, I32, I32, TP, I32, P, I32, U64, U32, U32, P, P, P]
+        L.pe_policy_math_host.argtypes = [I32, I32, P, P]
+        L.pe_policy_env_tile.argtypes = [P]
+        L.pe_policy_env_tile.restype = I32
+    for name in ("pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward",
+                 "pe_policy_forward_host", "pe_policy_math_host", "pe_create", "pe_destroy", "pe_seed", "pe_reset", "pe_step", "pe_get_info", "pe_get_state",
                  "pe_set_state", "pe_load_maps", "pe_synth_actions", "pe_poll_errors", "pe_pystream_create",
                  "pe_pystream_next", "pe_pystream_destroy", "pe_curriculum_enable", "pe_curriculum_disable",
                  "pe_curriculum_get", "pe_mcts_create", "pe_mcts_destroy", "pe_mcts_seed", "pe_mcts_set_rng",

@@ -1,0 +1,79 @@
+// tanh_ulp.cpp -- worst error of pe_tanhf (and pe_expf on the sampler's range) against f64
+// libm over ALL finite f32 inputs.  Stand-alone host program:
+//
+//   clang++ -O2 -std=c++17 -ffp-contract=off -pthread -o tanh_ulp tools/tanh_ulp.cpp && ./tanh_ulp
+//
+// Prints, for pe_tanhf, tau = max |pe_tanhf(x) - tanh(x)| / (2^-24 |tanh(x)|) -- the relative
+// error in units of u = 2^-24, the figure the error bound of tests/test_policy_host.py uses --
+// with the input that reaches it, and the same figure in ulps of the f32 result; for pe_expf
+// the same over [-87, 0].  DESIGN.md section 4 records the output.
+#include <cmath>
+#include <cstdio>
+#include <thread>
+#include <vector>
+
+#include "../rl-env_amd/csrc/pe_policy_math.hpp"
+
+struct Worst {
+  double rel = 0.0, ulp = 0.0;
+  float at_rel = 0.0f, at_ulp = 0.0f;
+};
+
+static double ulp_of(double exact) {
+  int e;
+  std::frexp(std::fabs(exact), &e);  // |exact| in [2^(e-1), 2^e)
+  if (e < -125) e = -125;            // subnormal spacing 2^-149
+  return std::ldexp(1.0, e - 24);
+}
+
+template <typename F, typename G>
+static Worst scan(uint32_t lo, uint32_t hi, F f, G ref) {  // bit patterns [lo, hi)
+  Worst w;
+  for (uint64_t u = lo; u < hi; ++u) {
+    const float x = pe_pol::bits_to_float((uint32_t)u);
+    if (!std::isfinite(x)) continue;
+    const double got = (double)f(x), exact = ref((double)x);
+    const double err = std::fabs(got - exact);
+    if (err == 0.0) continue;
+    const double rel = err / (std::ldexp(1.0, -24) * std::fabs(exact)), ul = err / ulp_of(exact);
+    if (rel > w.rel) w.rel = rel, w.at_rel = x;
+    if (ul > w.ulp) w.ulp = ul, w.at_ulp = x;
+  }
+  return w;
+}
+
+template <typename F, typename G>
+static Worst scan_all(uint32_t lo, uint64_t hi, F f, G ref) {
+  const unsigned nt = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+  std::vector<Worst> part(nt);
+  std::vector<std::thread> th;
+  const uint64_t span = (hi - lo + nt - 1) / nt;
+  for (unsigned i = 0; i < nt; ++i)
+    th.emplace_back([&, i] {
+      const uint64_t a = lo + i * span, b = std::min<uint64_t>(hi, a + span);
+      if (a < b) part[i] = scan((uint32_t)a, (uint32_t)b, f, ref);
+    });
+  for (auto& t : th) t.join();
+  Worst w;
+  for (const Worst& p : part) {
+    if (p.rel > w.rel) w.rel = p.rel, w.at_rel = p.at_rel;
+    if (p.ulp > w.ulp) w.ulp = p.ulp, w.at_ulp = p.at_ulp;
+  }
+  return w;
+}
+
+int main() {
+  // tanh is odd and pe_tanhf copies the sign bit: the positive half [0, +inf) covers both
+  const Worst t = scan_all(0x00000000u, 0x7F800000ull, [](float x) { return pe_pol::pe_tanhf(x); },
+                           [](double x) { return std::tanh(x); });
+  const Worst tn = scan_all(0x80000000u, 0xFF800000ull, [](float x) { return pe_pol::pe_tanhf(x); },
+                            [](double x) { return std::tanh(x); });
+  std::printf("pe_tanhf  x >= 0: tau = %.4f u at x = %.9g; %.4f ulp at x = %.9g\n", t.rel, t.at_rel, t.ulp, t.at_ulp);
+  std::printf("pe_tanhf  x <  0: tau = %.4f u at x = %.9g; %.4f ulp at x = %.9g\n", tn.rel, tn.at_rel, tn.ulp,
+              tn.at_ulp);
+  // pe_expf on [-87, 0] (the sampler's l_a - max l): bit patterns of -0.0 .. -87.0
+  const Worst e = scan_all(0x80000000u, (uint64_t)pe_pol::float_to_bits(-87.0f) + 1, [](float x) { return pe_pol::pe_expf(x); },
+                           [](double x) { return std::exp(x); });
+  std::printf("pe_expf [-87, 0]: %.4f u at x = %.9g; %.4f ulp at x = %.9g\n", e.rel, e.at_rel, e.ulp, e.at_ulp);
+  return 0;
+}
