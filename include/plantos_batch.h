@@ -377,10 +377,84 @@ int pe_policy_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe_poli
                            int32_t activation, const float* obs, int32_t mode, uint64_t seed,
                            uint32_t env_id_offset, uint32_t t, int32_t* actions, float* head0_or_null,
                            float* head1_or_null);
-/* pe_tanhf / pe_expf of n host floats (tests and the accuracy tool measure them). */
+/* pe_tanhf (which = 0) / pe_expf (1) / pe_sigmoidf (2) of n host floats (tests and the
+ * accuracy tool measure them). */
 int pe_policy_math_host(int32_t which, int32_t n, const float* x, float* y);
 /* Envs per workgroup of the forward kernel (introspection). */
 int32_t pe_policy_env_tile(const pe_policy* p);
+
+/* Recurrent policy inference: sb3_contrib's RecurrentActorCriticPolicy with n_lstm_layers = 1
+ * and no shared LSTM (RecurrentPPO("MlpLstmPolicy", policy_kwargs=dict(lstm_hidden_size=H,
+ * n_lstm_layers=1, enable_critic_lstm=True, net_arch=[128,128])), trainingCode.py:140-162;
+ * model.predict(obs, state=lstm_states, episode_start=episode_start, deterministic=True),
+ * trainingCode.py:413-434).  A recurrent policy is a pe_policy too: pe_policy_destroy and
+ * pe_policy_env_tile serve it; pe_policy_load / pe_policy_forward on it are PE_ERR_ARG, as
+ * are the *_lstm calls on a feed-forward policy.
+ *
+ * Definition (the host twin pe_policy_lstm_forward_host executes it literally; the kernel
+ * gives the same bits):
+ *  - 1 or 2 towers over the same obs row x[0..D).  Tower 0 is lstm_actor ->
+ *    mlp_extractor.policy_net -> action_net; tower 1, if present, is lstm_critic ->
+ *    mlp_extractor.value_net -> value_net (enable_critic_lstm=True).  Actor-only (1 tower)
+ *    is what predict() evaluates.  The critic as a Linear (enable_critic_lstm=False) and
+ *    shared_lstm=True are not supported.  Every tower has its own state (h, c) per env,
+ *    f32[H] each; H is the same for both towers, a multiple of 32 in 32..512.  After the
+ *    LSTM a tower is a tower of "Policy inference" above (1..3 hidden layers and a head,
+ *    the same width rules) whose first layer reads h' (K = H) instead of the obs.
+ *  - Episode start: a flag per env.  If it is set, h and c of every tower of that env read
+ *    as +0.0f in this step (SB3's (1 - episode_start) * state, as a select: no -0).
+ *  - Gate pre-activations, torch's layout: rows [0,H) i, [H,2H) f, [2H,3H) g, [3H,4H) o of
+ *    weight_ih_l0 [4H][D], weight_hh_l0 [4H][H], bias_ih_l0, bias_hh_l0 [4H].  Each is ONE
+ *    f32 chain: acc = bias_ih[j] + bias_hh[j] (one f32 add); acc = fmaf(w_ih[j][k], x[k],
+ *    acc) for k ascending over D; then acc = fmaf(w_hh[j][k], h[k], acc) for k ascending
+ *    over H.  No split-K (zero padding inside the chain is allowed).
+ *  - Cell: pe_sigmoidf(z) = fmaf(0.5f, pe_tanhf(0.5f * z), 0.5f);
+ *    c' = fmaf(sigma(z_f), c, sigma(z_i) * pe_tanhf(z_g)) (the product rounded once);
+ *    h' = sigma(z_o) * pe_tanhf(c').  (h', c') replace the env's state.
+ *  - The MLP, heads, argmax and sampler are those of "Policy inference", the Philox
+ *    counter layout and domain word included.
+ *
+ * pe_policy_lstm carries one tower's LSTM: its size and, for load / the host twin, tensors. */
+typedef struct pe_policy_lstm {
+    int32_t hidden;            /* H */
+    int32_t reserved[3];
+    const float* weight_ih;    /* f32[4H][D] (pe_policy_create_lstm ignores the tensors) */
+    const float* weight_hh;    /* f32[4H][H] */
+    const float* bias_ih;      /* f32[4H] */
+    const float* bias_hh;      /* f32[4H] */
+} pe_policy_lstm;
+
+/* Shapes only: allocates the packed device weights and the per-env state (both zeroed: a
+ * fresh policy's first forward behaves as an episode start) and chooses the env tile
+ * (env_tile as in pe_policy_create).  PE_ERR_ARG with a message if H is not a multiple of
+ * 32 in 32..512 (larger LSTMs need a K-streamed kernel this library does not have), or if
+ * a tile's images do not fit the 160 KiB of LDS (H = 512 needs env_tile 32). */
+int pe_policy_create_lstm(pe_handle* h, int32_t n_towers, const pe_policy_lstm* lstms, const pe_policy_tower* shapes,
+                          int32_t activation, int32_t env_tile, pe_policy** out);
+/* Repack the caller's DEVICE tensors: kernels only, asynchronous on `stream`, no allocation. */
+int pe_policy_load_lstm(pe_policy* p, const pe_policy_lstm* lstms, const pe_policy_tower* towers, void* stream);
+/* One recurrent forward of all n envs: obs / mode / seed / t / outputs as pe_policy_forward.
+ * start_a, start_b: device u8[n] or NULL; env e starts an episode if either flag is
+ * non-zero (the step's terminated and truncated buffers fit as they are).  Updates the
+ * policy's state in place.  One kernel, no host sync, no allocation: graph-capturable. */
+int pe_policy_forward_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* start_a_or_null,
+                           const uint8_t* start_b_or_null, int32_t mode, uint64_t seed, uint32_t t, int32_t* actions,
+                           float* head0_or_null, float* head1_or_null, void* stream);
+/* Zero the state of every env and tower (asynchronous on `stream`). */
+int pe_policy_lstm_reset_state(pe_policy* p, void* stream);
+/* Copy tower `tower`'s state to / from device tensors f32[n][H] (SB3's (1, n_envs, H));
+ * h or c may be NULL to skip it.  Asynchronous on `stream`. */
+int pe_policy_lstm_get_state(pe_policy* p, int32_t tower, float* h_or_null, float* c_or_null, void* stream);
+int pe_policy_lstm_set_state(pe_policy* p, int32_t tower, const float* h_or_null, const float* c_or_null,
+                             void* stream);
+/* The host twin on HOST arrays: obs f32[n][D]; start u8[n] or NULL; h_state / c_state
+ * f32[n_towers][n][H], updated in place; lstms / towers with host tensors; mode and outputs
+ * as pe_policy_forward_host. */
+int pe_policy_lstm_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe_policy_lstm* lstms,
+                                const pe_policy_tower* towers, int32_t activation, const float* obs,
+                                const uint8_t* start_or_null, float* h_state, float* c_state, int32_t mode,
+                                uint64_t seed, uint32_t env_id_offset, uint32_t t, int32_t* actions,
+                                float* head0_or_null, float* head1_or_null);
 
 /* Introspection for tests / benchmarks. */
 int32_t pe_num_envs(const pe_handle* h);

@@ -23,10 +23,11 @@ SRC_MCTS = os.path.join(HERE, "csrc", "pe_mcts.hip")
 SRC_RENDER = os.path.join(HERE, "csrc", "pe_render.hip")
 SRC_POLICY = os.path.join(HERE, "csrc", "pe_policy.hip")
 SRC_POLICY_HOST = os.path.join(HERE, "csrc", "pe_policy_host.cpp")
-SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST]
+SRC_POLICY_LSTM = os.path.join(HERE, "csrc", "pe_policy_lstm.hip")
+SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST, SRC_POLICY_LSTM]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in
                   ("pe_device.hpp", "pe_fast.hpp", "pe_quad.hpp", "pe_coop.hpp", "pe_handle.hpp", "pe_far.hpp",
-                   "pe_policy_math.hpp")] + [
+                   "pe_policy_math.hpp", "pe_policy_impl.hpp")] + [
     os.path.join(REPO, "include", "plantos_batch.h"), os.path.join(HERE, "tools_gen_lidar.py")]
 OUT = os.path.join(HERE, "plantos_amd", "libplantos_hip.so")
 OBJ_DIR = os.path.join(REPO, "build", "obj")

@@ -1,7 +1,8 @@
-// pe_policy_host.cpp -- the host twin of pe_policy_forward (include/plantos_batch.h,
-// "Policy inference"): the definition executed literally, one fmaf chain per
-// pre-activation in ascending k, pe_tanhf / pe_expf / the sampler from the header the
-// kernel includes too.  Plain C++: no handle, no device.
+// pe_policy_host.cpp -- the host twins of pe_policy_forward and pe_policy_forward_lstm
+// (include/plantos_batch.h, "Policy inference" and "Recurrent policy inference"): the
+// definitions executed literally, one fmaf chain per pre-activation in ascending k,
+// pe_tanhf / pe_sigmoidf / pe_expf / the sampler from the header the kernels include too.
+// Plain C++: no handle, no device.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -29,6 +30,24 @@ extern "C" int pe_internal_policy_check(int32_t n_towers, const pe_policy_tower*
     if (with_ptrs)
       for (int l = 0; l <= t.n_hidden; ++l)
         if (!t.weight[l] || !t.bias[l]) return fail("null weight or bias tensor");
+  }
+  return PE_OK;
+}
+
+// Shape rules of the LSTMs of a recurrent policy (shared with pe_policy_lstm.hip).
+extern "C" int pe_internal_policy_lstm_check(int32_t n_towers, const pe_policy_lstm* ls, int with_ptrs) {
+  auto fail = [](const std::string& m) { return pe_internal_set_error(PE_ERR_ARG, m.c_str()); };
+  if (!ls) return fail("null lstms");
+  if (n_towers < 1 || n_towers > 2) return fail("a policy has 1 or 2 towers");
+  for (int i = 0; i < n_towers; ++i) {
+    const int H = ls[i].hidden;
+    if (H > 512)
+      return fail("lstm hidden size " + std::to_string(H) + " > 512: the h tile no longer fits LDS beside the obs "
+                  "tile; that needs a K-streamed GEMM kernel, which this library does not have");
+    if (H < 32 || (H & 31)) return fail("lstm hidden size must be a multiple of 32 in 32..512");
+    if (H != ls[0].hidden) return fail("both towers' LSTMs must have the same hidden size");
+    if (with_ptrs && (!ls[i].weight_ih || !ls[i].weight_hh || !ls[i].bias_ih || !ls[i].bias_hh))
+      return fail("null lstm tensor");
   }
   return PE_OK;
 }
@@ -97,6 +116,54 @@ void tower_forward(const pe_policy_tower& t, int D, int activation, const float*
     tower_body<false>(t, D, activation, x, out);
 }
 
+// One LSTM step of one env: (h, c) f32[H] are replaced; `start` reads them as +0.  Two units'
+// four gates run side by side (each still one chain: bias sum, x in k order, h in k order).
+template <bool HW>
+__attribute__((always_inline)) inline void lstm_body(const pe_policy_lstm& L, int D, const float* x, bool start,
+                                                     float* h, float* c) {
+#pragma clang fp contract(off)
+  const int H = L.hidden;
+  float h_old[512];
+  for (int k = 0; k < H; ++k) h_old[k] = start ? 0.0f : h[k];
+  for (int j = 0; j < H; j += 2) {
+    float acc[8];
+    const float *wi[8], *wh[8];
+    for (int q = 0; q < 8; ++q) {
+      const size_t row = (size_t)(q & 3) * H + j + (q >> 2);
+      acc[q] = L.bias_ih[row] + L.bias_hh[row];
+      wi[q] = L.weight_ih + row * D;
+      wh[q] = L.weight_hh + row * H;
+    }
+    for (int k = 0; k < D; ++k)
+      for (int q = 0; q < 8; ++q) acc[q] = HW ? __builtin_fmaf(wi[q][k], x[k], acc[q]) : std::fmaf(wi[q][k], x[k], acc[q]);
+    for (int k = 0; k < H; ++k)
+      for (int q = 0; q < 8; ++q)
+        acc[q] = HW ? __builtin_fmaf(wh[q][k], h_old[k], acc[q]) : std::fmaf(wh[q][k], h_old[k], acc[q]);
+    for (int u = 0; u < 2; ++u)
+      pe_lstm_cell(acc[4 * u], acc[4 * u + 1], acc[4 * u + 2], acc[4 * u + 3], start ? 0.0f : c[j + u], &h[j + u],
+                   &c[j + u]);
+  }
+}
+
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+__attribute__((target("fma"))) void lstm_step_hw(const pe_policy_lstm& L, int D, const float* x, bool start, float* h,
+                                                 float* c) {
+  lstm_body<true>(L, D, x, start, h, c);
+}
+#else
+void lstm_step_hw(const pe_policy_lstm& L, int D, const float* x, bool start, float* h, float* c) {
+  lstm_body<false>(L, D, x, start, h, c);
+}
+#endif
+
+void lstm_step(const pe_policy_lstm& L, int D, const float* x, bool start, float* h, float* c) {
+  static const bool hw = have_hw_fma();
+  if (hw)
+    lstm_step_hw(L, D, x, start, h, c);
+  else
+    lstm_body<false>(L, D, x, start, h, c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -125,10 +192,40 @@ int pe_policy_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe_poli
   return PE_OK;
 }
 
+int pe_policy_lstm_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe_policy_lstm* lstms,
+                                const pe_policy_tower* towers, int32_t activation, const float* obs,
+                                const uint8_t* start, float* h_state, float* c_state, int32_t mode, uint64_t seed,
+                                uint32_t env_id_offset, uint32_t t, int32_t* actions, float* head0, float* head1) {
+  if (const int rc = pe_internal_policy_check(n_towers, towers, activation, 1)) return rc;
+  if (const int rc = pe_internal_policy_lstm_check(n_towers, lstms, 1)) return rc;
+  if (n < 0 || D < 1 || !obs || !actions || !h_state || !c_state)
+    return pe_internal_set_error(PE_ERR_ARG, "bad n / D or null obs / actions / state");
+  if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
+    return pe_internal_set_error(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
+  if (head1 && n_towers < 2) return pe_internal_set_error(PE_ERR_ARG, "head1 needs a second tower");
+  const int A = towers[0].n_out, H = lstms[0].hidden;
+  for (int e = 0; e < n; ++e) {
+    const float* x = obs + (size_t)e * D;
+    const bool st = start && start[e];
+    float l[8], v;
+    for (int ti = 0; ti < n_towers; ++ti) {
+      float* h = h_state + ((size_t)ti * n + e) * H;
+      float* c = c_state + ((size_t)ti * n + e) * H;
+      lstm_step(lstms[ti], D, x, st, h, c);
+      tower_forward(towers[ti], H, activation, h, ti == 0 ? l : &v);
+    }
+    if (n_towers == 2 && head1) head1[e] = v;
+    if (head0) std::memcpy(head0 + (size_t)e * A, l, sizeof(float) * A);
+    actions[e] = mode == PE_POLICY_ARGMAX ? policy_argmax(l, A)
+                                          : policy_sample(l, A, policy_uniform(seed, env_id_offset + (uint32_t)e, t));
+  }
+  return PE_OK;
+}
+
 int pe_policy_math_host(int32_t which, int32_t n, const float* x, float* y) {
-  if (n < 0 || (n > 0 && (!x || !y)) || which < 0 || which > 1)
-    return pe_internal_set_error(PE_ERR_ARG, "which must be 0 (pe_tanhf) or 1 (pe_expf); null argument");
-  for (int i = 0; i < n; ++i) y[i] = which == 0 ? pe_tanhf(x[i]) : pe_expf(x[i]);
+  if (n < 0 || (n > 0 && (!x || !y)) || which < 0 || which > 2)
+    return pe_internal_set_error(PE_ERR_ARG, "which must be 0 (pe_tanhf), 1 (pe_expf) or 2 (pe_sigmoidf); null argument");
+  for (int i = 0; i < n; ++i) y[i] = which == 0 ? pe_tanhf(x[i]) : (which == 1 ? pe_expf(x[i]) : pe_sigmoidf(x[i]));
   return PE_OK;
 }
 

@@ -1,0 +1,278 @@
+// pe_policy_impl.hpp -- what the two policy translation units share (pe_policy.hip: the
+// feed-forward policy; pe_policy_lstm.hip: the recurrent one): the pe_policy object, the
+// layer tables, the MFMA hidden layer, the weight packing kernel and the host helpers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/plantos_batch.h"
+#include "pe_handle.hpp"
+#include "pe_policy_math.hpp"
+
+extern "C" int pe_internal_policy_check(int32_t n_towers, const pe_policy_tower* tw, int32_t activation,
+                                        int with_ptrs);
+extern "C" int pe_internal_policy_lstm_check(int32_t n_towers, const pe_policy_lstm* ls, int with_ptrs);
+
+namespace pe_pol {
+
+constexpr int kThreads = 512, kWaves = kThreads / 64;
+constexpr int kMaxLds = 160 * 1024;
+constexpr int kHeadRows = 9;  // tower 0's <= 8 outputs + the value
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Layer {
+  int K, Kp, N;            // inputs, inputs padded to a multiple of 8 (hidden layers), outputs
+  uint32_t off_w, off_b;   // float offsets into the packed buffer
+};
+struct Tower {
+  int n_hidden, n_out;
+  Layer l[4];  // hidden layers, then the head
+};
+
+struct PackLayer {
+  const float* w;
+  const float* b;
+  int K, Kp, N, head;
+  uint32_t off_w, off_b, n_w;  // n_w: packed weight floats
+};
+struct PackArgs {
+  float* packed;
+  PackLayer l[8];
+};
+
+}  // namespace pe_pol
+
+struct pe_policy {
+  pe_handle* h;
+  int n_towers, act, env_tile;
+  int D, SD, Kp0, HB;
+  pe_pol::Tower tw[2];
+  float* mem;        // packed weights, then the code table
+  size_t n_packed;   // floats
+  size_t lds;
+  // recurrent policies only (H = 0: feed-forward)
+  int H;                   // LSTM hidden size
+  uint32_t off_lw[2];      // packed gate weights of tower i: [unit tile][k group][gate][lane][4]
+  uint32_t off_lb[2];      // bias_ih + bias_hh of tower i: [4H]
+  float* state;            // [tower][h, c][env tile][H][env_tile]
+  size_t n_state;          // floats of one (tower, h or c) image: tiles * H * env_tile
+};
+
+namespace {
+using namespace pe_pol;
+
+// Packed hidden weights: [neuron tile jt][k group kg][lane][q], element = W[jt*32 + (lane & 31)]
+// [kg*8 + q*2 + (lane >> 5)] (0 for k >= K): float4 q = 0..3 of a lane are its A operands of
+// four consecutive 32x32x2 k-steps.  Head weights and all biases keep their layout.
+__global__ __launch_bounds__(256) void pe_policy_pack_kernel(PackArgs a) {
+  const PackLayer& L = a.l[blockIdx.y];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < L.n_w) {
+    float v;
+    if (L.head) {
+      v = L.w[i];
+    } else {
+      const uint32_t q = i & 3u, lane = (i >> 2) & 63u, blk = i >> 8, KG = (uint32_t)L.Kp >> 3;
+      const uint32_t kg = blk % KG, jt = blk / KG;
+      const uint32_t j = jt * 32u + (lane & 31u), k = kg * 8u + q * 2u + (lane >> 5);
+      v = k < (uint32_t)L.K ? L.w[(size_t)j * L.K + k] : 0.0f;
+    }
+    a.packed[L.off_w + i] = v;
+  } else if (i < L.n_w + (uint32_t)L.N) {
+    a.packed[L.off_b + (i - L.n_w)] = L.b[i - L.n_w];
+  }
+}
+
+__device__ __forceinline__ float activate(float z, int act) { return act == PE_ACT_TANH ? pe_tanhf(z) : pe_relu(z); }
+
+// out[j][e] = act(b_j + sum_k W[j][k] in[k][e]) for the tile's E = 32 * ET envs; in / out are
+// LDS images [k][E] / [j][E].  T is the operand type (only float is defined and built).
+template <int ET, typename T>
+__device__ __forceinline__ void hidden_layer(const T* __restrict__ wp, const float* __restrict__ bias,
+                                             const T* in, T* out, int KG, int NT, int act) {
+  constexpr int E = 32 * ET;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
+  for (int jt = wave; jt < NT; jt += kWaves) {
+    f32x16 acc[ET];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float b = bias[jt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+#pragma unroll
+      for (int et = 0; et < ET; ++et) acc[et][r] = b;
+    }
+    const float4* w4 = reinterpret_cast<const float4*>(wp) + (size_t)jt * KG * 64 + lane;
+    const T* xin = in + half * E + col;
+    float4 w = w4[0];
+    for (int kg = 0; kg < KG; ++kg) {
+      const float4 wn = w4[(size_t)min(kg + 1, KG - 1) * 64];  // the next group's, in flight over the MFMAs
+      const T* x = xin + kg * 8 * E;
+      const float wq[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int et = 0; et < ET; ++et)
+          acc[et] = __builtin_amdgcn_mfma_f32_32x32x2f32(wq[q], x[q * 2 * E + et * 32], acc[et], 0, 0, 0);
+      }
+      w = wn;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int j = jt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+#pragma unroll
+      for (int et = 0; et < ET; ++et) out[j * E + et * 32 + col] = activate(acc[et][r], act);
+    }
+  }
+}
+
+// The tile's obs rows -> the staging image [env][SD] (LDS, `stage`) -> xT[k][env], k padded
+// with zeros to Kp0, rows of envs past n zero.  Ends with a barrier.
+template <int E>
+__device__ __forceinline__ void stage_obs(const void* obs, int obs_is_codes, const float* tab_g, float* tab,
+                                          float* stage, float* xT, int64_t e0, int rows, int D, int SD, int Kp0) {
+  const int tid = threadIdx.x;
+  const int count = rows * D;
+  if (obs_is_codes) {
+    if (tid < 256) tab[tid] = tab_g[tid];
+    __syncthreads();
+    const uint8_t* src = static_cast<const uint8_t*>(obs) + e0 * D;
+    for (int i = tid; i < count; i += kThreads) {
+      const int row = i / D;
+      stage[row * SD + (i - row * D)] = tab[src[i]];
+    }
+  } else {
+    const float* src = static_cast<const float*>(obs) + e0 * D;
+    for (int i = tid; i < count; i += kThreads) {
+      const int row = i / D;
+      stage[row * SD + (i - row * D)] = src[i];
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < Kp0 * E; idx += kThreads) {
+    const int k = idx / E, e = idx - k * E;
+    xT[idx] = (k < D && e < rows) ? stage[e * SD + k] : 0.0f;
+  }
+  __syncthreads();
+}
+
+// Head of a tower (<= 8 + 1 outputs): VALU fmaf chains, one (env, output) per lane, over the
+// last hidden buffer `in` [K][E]; row `o` of tower 0 / the last row of tower 1 in hd.
+template <int E>
+__device__ __forceinline__ void head_layer(const float* packed, const Layer& H, int n_out, int ti, const float* in,
+                                           float* hd) {
+  for (int idx = threadIdx.x; idx < n_out * E; idx += kThreads) {
+    const int o = idx / E, e = idx - o * E;
+    const float* w = packed + H.off_w + (size_t)o * H.K;
+    float acc = packed[H.off_b + o];
+    for (int k = 0; k < H.K; ++k) acc = fmaf(w[k], in[k * E + e], acc);
+    hd[(ti == 0 ? o : kHeadRows - 1) * E + e] = acc;
+  }
+}
+
+// Action + outputs of env e0 + tid from the head rows in hd.
+template <int E>
+__device__ __forceinline__ void act_and_store(const float* hd, int A, int rows, int64_t e0, int mode, uint64_t seed,
+                                              uint32_t env_off, uint32_t t, int32_t* actions, float* head0,
+                                              float* head1) {
+  const int tid = threadIdx.x;
+  if (tid < rows) {
+    const int64_t e = e0 + tid;
+    float l[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) l[q] = q < A ? hd[q * E + tid] : 0.0f;
+    int act;
+    if (mode == PE_POLICY_ARGMAX)
+      act = policy_argmax(l, A);
+    else
+      act = policy_sample(l, A, policy_uniform(seed, env_off + (uint32_t)e, t));
+    actions[e] = act;
+    if (head0) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (q < A) head0[e * A + q] = l[q];
+    }
+    if (head1) head1[e] = hd[(kHeadRows - 1) * E + tid];
+  }
+}
+
+// ---------------------------------------------------------------- host side
+inline int fail(int code, const std::string& msg) { return pe_internal_set_error(code, msg.c_str()); }
+
+inline int hip_fail(hipError_t e, const char* what) {
+  return fail(PE_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+struct DevBind {
+  int prev = -1;
+  hipError_t err = hipSuccess;
+  explicit DevBind(int dev) {
+    (void)hipGetLastError();  // drop a stale error of an earlier call (launch checks below)
+    int cur = -1;
+    err = hipGetDevice(&cur);
+    if (err == hipSuccess && cur != dev) {
+      err = hipSetDevice(dev);
+      if (err == hipSuccess) prev = cur;
+    }
+  }
+  ~DevBind() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+// Fills p's layer tables of `n_towers` towers whose first layer reads K0 inputs, packed from
+// float offset `off` on; returns the end offset and the widest hidden layer.
+inline size_t layout_towers(pe_policy* p, int n_towers, const pe_policy_tower* shapes, int K0, size_t off, int* hmax) {
+  *hmax = 0;
+  for (int i = 0; i < n_towers; ++i) {
+    Tower& t = p->tw[i];
+    t.n_hidden = shapes[i].n_hidden;
+    t.n_out = shapes[i].n_out;
+    int K = K0;
+    for (int l = 0; l <= t.n_hidden; ++l) {
+      Layer& L = t.l[l];
+      const bool head = l == t.n_hidden;
+      L.K = K;
+      L.Kp = head ? K : (K + 7) & ~7;
+      L.N = head ? t.n_out : shapes[i].hidden[l];
+      L.off_w = (uint32_t)off;
+      off += (size_t)L.N * L.Kp;
+      L.off_b = (uint32_t)off;
+      off += ((size_t)L.N + 3) & ~(size_t)3;  // every offset stays a multiple of 16 B
+      if (!head) *hmax = *hmax > L.N ? *hmax : L.N;
+      K = L.N;
+    }
+  }
+  return off;
+}
+
+// The pack arguments of p's MLP layers from the caller's device tensors; PE_OK or PE_ERR_ARG.
+inline int pack_towers(const pe_policy* p, const pe_policy_tower* towers, PackArgs* a, int* nl, uint32_t* most) {
+  a->packed = p->mem;
+  *nl = 0;
+  *most = 0;
+  for (int i = 0; i < p->n_towers; ++i) {
+    const Tower& t = p->tw[i];
+    if (towers[i].n_hidden != t.n_hidden || towers[i].n_out != t.n_out)
+      return fail(PE_ERR_ARG, "tower shape differs from pe_policy_create's");
+    for (int l = 0; l <= t.n_hidden; ++l) {
+      if (l < t.n_hidden && towers[i].hidden[l] != t.l[l].N)
+        return fail(PE_ERR_ARG, "tower shape differs from pe_policy_create's");
+      if (!towers[i].weight[l] || !towers[i].bias[l]) return fail(PE_ERR_ARG, "null weight or bias tensor");
+      PackLayer& L = a->l[(*nl)++];
+      L.w = towers[i].weight[l];
+      L.b = towers[i].bias[l];
+      L.K = t.l[l].K;
+      L.Kp = t.l[l].Kp;
+      L.N = t.l[l].N;
+      L.head = l == t.n_hidden;
+      L.off_w = t.l[l].off_w;
+      L.off_b = t.l[l].off_b;
+      L.n_w = (uint32_t)(L.N * L.Kp);
+      *most = *most > L.n_w + (uint32_t)L.N ? *most : L.n_w + (uint32_t)L.N;
+    }
+  }
+  return PE_OK;
+}
+
+}  // namespace

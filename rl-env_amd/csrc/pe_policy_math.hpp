@@ -91,6 +91,24 @@ PE_HD float pe_tanhf(float x) {
 
 PE_HD float pe_relu(float z) { return z > 0.0f ? z : 0.0f; }
 
+// sigmoid(z) = 1/2 + 1/2 tanh(z / 2): no division of its own, results 0, 1 or in
+// [2^-25, 1 - 2^-25] (never subnormal); NaN passes through.
+PE_HD float pe_sigmoidf(float z) {
+#pragma clang fp contract(off)
+  return fmaf(0.5f, pe_tanhf(0.5f * z), 0.5f);
+}
+
+// The LSTM cell of the recurrent policy from its four gate pre-activations and the old cell
+// state: c' = sigma(z_f) c + sigma(z_i) tanh(z_g) (the product rounded, then one fmaf),
+// h' = sigma(z_o) tanh(c').
+PE_HD void pe_lstm_cell(float zi, float zf, float zg, float zo, float c, float* h_new, float* c_new) {
+#pragma clang fp contract(off)
+  const float ig = pe_sigmoidf(zi) * pe_tanhf(zg);
+  const float cn = fmaf(pe_sigmoidf(zf), c, ig);
+  *c_new = cn;
+  *h_new = pe_sigmoidf(zo) * pe_tanhf(cn);
+}
+
 // Philox4x32-10, the counter / key layout of the env's generator (pe_device.hpp,
 // oracle/plantos_oracle.c); written with 64-bit products so host and device share it.
 struct U4 {

@@ -5,9 +5,10 @@ Public surface:
   PlantOSVecEnv     Stable-Baselines3 VecEnv drop-in for DummyVecEnv (A2C_training.py:216-218)
   PlantOSVectorEnv  gymnasium-0.29 VectorEnv convention over the same batch
   Policy            batched MLP policy inference on the device: obs (codes or f32) -> actions
+  RecurrentPolicy   the same for LSTM policies (sb3_contrib MlpLstmPolicy), state on the device
 """
 from .batch import PlantOSBatch  # noqa: F401
-from .policy import Policy  # noqa: F401
+from .policy import Policy, RecurrentPolicy  # noqa: F401
 from .vec_env import PlantOSVecEnv, PlantOSVectorEnv  # noqa: F401
 
-__all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy"]
+__all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy"]

@@ -44,6 +44,8 @@ EXPORTS = [
     "pe_render_tables", "pe_render",
     "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward", "pe_policy_forward_host",
     "pe_policy_math_host", "pe_policy_env_tile",
+    "pe_policy_create_lstm", "pe_policy_load_lstm", "pe_policy_forward_lstm", "pe_policy_lstm_reset_state",
+    "pe_policy_lstm_get_state", "pe_policy_lstm_set_state", "pe_policy_lstm_forward_host",
 ]
 PE_ACT_TANH, PE_ACT_RELU = 0, 1
 PE_POLICY_ARGMAX, PE_POLICY_SAMPLE = 0, 1
@@ -67,6 +69,13 @@ class PEPolicyTower(ctypes.Structure):
     _fields_ = [
         ("n_hidden", ctypes.c_int32), ("hidden", ctypes.c_int32 * 3), ("n_out", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 3), ("weight", ctypes.c_void_p * 4), ("bias", ctypes.c_void_p * 4),
+    ]
+
+
+class PEPolicyLstm(ctypes.Structure):
+    _fields_ = [
+        ("hidden", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3), ("weight_ih", ctypes.c_void_p),
+        ("weight_hh", ctypes.c_void_p), ("bias_ih", ctypes.c_void_p), ("bias_hh", ctypes.c_void_p),
     ]
 
 
@@ -148,7 +157,18 @@ def lib():
         L.pe_policy_math_host.argtypes = [I32, I32, P, P]
         L.pe_policy_env_tile.argtypes = [P]
         L.pe_policy_env_tile.restype = I32
-    for name in ("pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward",
+    if hasattr(L, "pe_policy_create_lstm"):  # (an older library loaded for a same-box A/B lacks them)
+        TP, LP = ctypes.POINTER(PEPolicyTower), ctypes.POINTER(PEPolicyLstm)
+        L.pe_policy_create_lstm.argtypes = [P, I32, LP, TP, I32, I32, ctypes.POINTER(P)]
+        L.pe_policy_load_lstm.argtypes = [P, LP, TP, P]
+        L.pe_policy_forward_lstm.argtypes = [P, P, I32, P, P, I32, U64, U32, P, P, P, P]
+        L.pe_policy_lstm_reset_state.argtypes = [P, P]
+        L.pe_policy_lstm_get_state.argtypes = [P, I32, P, P, P]
+        L.pe_policy_lstm_set_state.argtypes = [P, I32, P, P, P]
+        L.pe_policy_lstm_forward_host.argtypes = [I32, I32, I32, LP, TP, I32, P, P, P, P, I32, U64, U32, U32, P, P, P]
+    for name in ("pe_policy_create_lstm", "pe_policy_load_lstm", "pe_policy_forward_lstm",
+                 "pe_policy_lstm_reset_state", "pe_policy_lstm_get_state", "pe_policy_lstm_set_state",
+                 "pe_policy_lstm_forward_host", "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward",
                  "pe_policy_forward_host", "pe_policy_math_host", "pe_create", "pe_destroy", "pe_seed", "pe_reset", "pe_step", "pe_get_info", "pe_get_state",
                  "pe_set_state", "pe_load_maps", "pe_synth_actions", "pe_poll_errors", "pe_pystream_create",
                  "pe_pystream_next", "pe_pystream_destroy", "pe_curriculum_enable", "pe_curriculum_disable",

@@ -12,6 +12,17 @@ device.  Learners stay out of scope: `Policy.load` takes the weights a learner p
     for _ in range(steps):
         actions, logits, values = policy.act()      # reads the batch's current obs
         obs, rewards, dones, infos = venv.step(actions)
+
+RecurrentPolicy is the same stage for sb3_contrib's RecurrentPPO("MlpLstmPolicy") with one
+LSTM layer per tower (trainingCode.py:140-162): the LSTM state lives on the device, and the
+episode-start flags are the step's own terminated / truncated tensors.
+
+    policy = RecurrentPolicy.from_state_dict(batch, model.policy.state_dict())
+    batch.reset()
+    actions, _, _ = policy.act()                    # zero state: an episode start
+    for _ in range(steps):
+        obs, rewards, terminated, truncated = batch.step(actions)
+        actions, logits, values = policy.act(episode_start=(terminated, truncated))
 """
 import ctypes
 import re
@@ -156,11 +167,12 @@ def host_forward(towers, tensors, activation, obs, deterministic=True, seed=0, e
 
 
 def math_host(which, x):
-    """pe_tanhf ("tanh") or pe_expf ("exp") of a float32 array, as the twin and the kernel compute them."""
+    """pe_tanhf ("tanh"), pe_expf ("exp") or pe_sigmoidf ("sigmoid") of a float32 array, as the
+    twins and the kernels compute them."""
     x = np.ascontiguousarray(x, np.float32)
     y = np.empty_like(x)
     P = ctypes.c_void_p
-    C.check(C.lib().pe_policy_math_host({"tanh": 0, "exp": 1}[which], x.size, x.ctypes.data_as(P),
+    C.check(C.lib().pe_policy_math_host({"tanh": 0, "exp": 1, "sigmoid": 2}[which], x.size, x.ctypes.data_as(P),
                                         y.ctypes.data_as(P)), "pe_policy_math_host")
     return y
 
@@ -311,3 +323,345 @@ class Policy:
             raise ValueError("no weights loaded")
         return host_forward(self.towers, tensors, self.activation, obs_np, deterministic=deterministic,
                             seed=self.seed, env_id_offset=int(self.batch.cfg.env_id_offset), t=t)
+
+
+# ------------------------------------------------------------------ recurrent policy
+LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def check_lstm_hidden(hidden):
+    """ValueError unless `hidden` is an LSTM size the kernel evaluates: a multiple of 32 in 32..512."""
+    hidden = int(hidden)
+    if hidden > 512:
+        raise ValueError(f"lstm hidden size {hidden} > 512 is not supported: the h tile no longer fits LDS "
+                         "(that needs a K-streamed GEMM kernel)")
+    if hidden < 32 or hidden % 32:
+        raise ValueError(f"lstm hidden size must be a multiple of 32 in 32..512, got {hidden}")
+    return hidden
+
+
+def parse_lstm_state_dict(sd, activation=None):
+    """(H, towers, activation, lstm_tensors, mlp_tensors) of an sb3_contrib
+    RecurrentActorCriticPolicy state dict with n_lstm_layers=1 and no shared LSTM:
+
+    lstm_actor.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}, mlp_extractor.policy_net.*,
+    action_net -> tower 0; lstm_critic.*, mlp_extractor.value_net.*, value_net -> tower 1
+    (enable_critic_lstm=True).  A dict without lstm_critic.* and value nets is an actor-only
+    policy (what predict() evaluates).  lstm_tensors[i] = (w_ih, w_hh, b_ih, b_hh);
+    mlp_tensors[i] = [(weight, bias), ..] as parse_state_dict returns them.  ValueError for the
+    critic as a Linear (critic.weight: enable_critic_lstm=False, also what shared_lstm=True
+    leaves), more LSTM layers (*_l1 keys), a shared trunk, unsupported widths or shapes that
+    do not chain.  Tanh unless told otherwise."""
+    keys = list(sd)
+    if any(k.startswith("critic.") for k in keys):
+        raise ValueError("the critic as a Linear layer (critic.*: enable_critic_lstm=False or shared_lstm=True) "
+                         "is not supported: enable_critic_lstm=True or an actor-only dict")
+    if any(re.fullmatch(r"lstm_(actor|critic)\..*_l[1-9]\d*(_reverse)?", k) for k in keys):
+        raise ValueError("n_lstm_layers > 1 (or a bidirectional LSTM) is not supported")
+    if any(k.startswith("mlp_extractor.shared_net") for k in keys):
+        raise ValueError("shared-trunk policies (mlp_extractor.shared_net) are not supported")
+    if not any(k.startswith("lstm_actor.") for k in keys):
+        raise ValueError("unrecognised state dict: expected lstm_actor.* (RecurrentActorCriticPolicy)")
+    critic = any(k.startswith("lstm_critic.") for k in keys)
+    need = [f"lstm_actor.{k}" for k in LSTM_KEYS] + ["action_net.weight", "action_net.bias"]
+    if critic:
+        need += [f"lstm_critic.{k}" for k in LSTM_KEYS] + ["value_net.weight", "value_net.bias"]
+    for k in need:
+        if k not in sd:
+            raise ValueError(f"state dict lacks {k}")
+    lstm = [tuple(sd[f"lstm_actor.{k}"] for k in LSTM_KEYS)]
+    mlp = [_linears(sd, "mlp_extractor.policy_net") + [(sd["action_net.weight"], sd["action_net.bias"])]]
+    if critic:
+        lstm.append(tuple(sd[f"lstm_critic.{k}"] for k in LSTM_KEYS))
+        mlp.append(_linears(sd, "mlp_extractor.value_net") + [(sd["value_net.weight"], sd["value_net.bias"])])
+    if lstm[0][1].dim() != 2:
+        raise ValueError("lstm_actor.weight_hh_l0 must be a matrix")
+    H = check_lstm_hidden(lstm[0][1].shape[1])
+    D = lstm[0][0].shape[1] if lstm[0][0].dim() == 2 else -1
+    for w_ih, w_hh, b_ih, b_hh in lstm:
+        if (tuple(w_ih.shape) != (4 * H, D) or tuple(w_hh.shape) != (4 * H, H) or tuple(b_ih.shape) != (4 * H,)
+                or tuple(b_hh.shape) != (4 * H,)):
+            raise ValueError("lstm shapes do not chain (both towers need the same hidden size and obs length)")
+    for tw in mlp:
+        if len(tw) < 2:
+            raise ValueError("a tower needs at least one hidden layer after the LSTM (net_arch)")
+        k = H
+        for w, b in tw:
+            if w.dim() != 2 or b.dim() != 1 or w.shape[0] != b.shape[0] or w.shape[1] != k:
+                raise ValueError("layer shapes do not chain")
+            k = w.shape[0]
+    towers = check_towers([[w.shape[0] for w, _ in tw] for tw in mlp])
+    return H, towers, (activation or "tanh"), lstm, mlp
+
+
+def _lstm_structs(hidden, n_towers, tensors=None, keep=None):
+    arr = (C.PEPolicyLstm * n_towers)()
+    for i in range(n_towers):
+        arr[i].hidden = hidden
+        if tensors is None:
+            continue
+        for name, x in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), tensors[i]):
+            setattr(arr[i], name, x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())
+            if keep is not None:
+                keep.append(x)
+    return arr
+
+
+def _check_lstm_shapes(hidden, n_towers, lstm_tensors, obs_dim):
+    if len(lstm_tensors) != n_towers:
+        raise ValueError(f"expected {n_towers} towers of lstm tensors, got {len(lstm_tensors)}")
+    want = ((4 * hidden, obs_dim), (4 * hidden, hidden), (4 * hidden,), (4 * hidden,))
+    for i, tw in enumerate(lstm_tensors):
+        if len(tw) != 4 or any(tuple(x.shape) != w for x, w in zip(tw, want)):
+            raise ValueError(f"tower {i}: expected lstm tensors (w_ih, w_hh, b_ih, b_hh) of shapes {want}")
+
+
+def lstm_host_forward(hidden, towers, lstm_tensors, mlp_tensors, activation, obs, states=None, episode_start=None,
+                      deterministic=True, seed=0, env_id_offset=0, t=0):
+    """The host twin of the recurrent policy (pe_policy_lstm_forward_host), no device.  obs f32
+    [n, D]; states: [(h, c), ..] per tower, f32 [n, H] each (None: zeros); episode_start: bool /
+    u8 [n] or None.  Returns ((actions, logits, values or None), new_states) as numpy arrays;
+    the inputs are left as they are."""
+    hidden = check_lstm_hidden(hidden)
+    towers = check_towers(towers)
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
+    obs = np.ascontiguousarray(obs, np.float32)
+    if obs.ndim != 2:
+        raise ValueError("obs must be [n, D]")
+    n, D = obs.shape
+    nt = len(towers)
+    f32 = lambda x: np.ascontiguousarray(_np(x), np.float32)  # noqa: E731
+    lt = [tuple(f32(x) for x in tw) for tw in lstm_tensors]
+    mt = [[(f32(w), f32(b)) for w, b in tw] for tw in mlp_tensors]
+    _check_lstm_shapes(hidden, nt, lt, D)
+    _check_tensor_shapes(towers, mt, hidden)
+    hs = np.zeros((nt, n, hidden), np.float32)
+    cs = np.zeros((nt, n, hidden), np.float32)
+    if states is not None:
+        if len(states) != nt:
+            raise ValueError(f"expected {nt} (h, c) pairs")
+        for i, (h, c) in enumerate(states):
+            h, c = f32(h), f32(c)
+            if h.shape != (n, hidden) or c.shape != (n, hidden):
+                raise ValueError(f"states must be [n, H] = {(n, hidden)}")
+            hs[i], cs[i] = h, c
+    start = None
+    if episode_start is not None:
+        start = np.ascontiguousarray(np.asarray(_np(episode_start)) != 0, np.uint8)
+        if start.shape != (n,):
+            raise ValueError("episode_start must be [n]")
+    keep = []
+    larr = _lstm_structs(hidden, nt, lt, keep)
+    tarr = _tower_structs(towers, mt, keep)
+    A = towers[0][-1]
+    actions = np.zeros(n, np.int32)
+    logits = np.zeros((n, A), np.float32)
+    values = np.zeros(n, np.float32) if nt == 2 else None
+    P = ctypes.c_void_p
+    C.check(C.lib().pe_policy_lstm_forward_host(
+        n, D, nt, larr, tarr, ACTIVATIONS[activation], obs.ctypes.data_as(P),
+        start.ctypes.data_as(P) if start is not None else None, hs.ctypes.data_as(P), cs.ctypes.data_as(P),
+        C.PE_POLICY_ARGMAX if deterministic else C.PE_POLICY_SAMPLE, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        int(env_id_offset) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, actions.ctypes.data_as(P), logits.ctypes.data_as(P),
+        values.ctypes.data_as(P) if values is not None else None), "pe_policy_lstm_forward_host")
+    return (actions, logits, values), [(hs[i], cs[i]) for i in range(nt)]
+
+
+class RecurrentPolicy:
+    """An LSTM policy (sb3_contrib MlpLstmPolicy, one LSTM layer per tower) over the obs of a
+    PlantOSBatch (or of a PlantOSVecEnv's batch).
+
+    hidden: the LSTM size H (a multiple of 32 in 32..512); towers: the MLP after the LSTM,
+    [[h1, .., A], [h1, .., 1]] (actor and critic, each with its own LSTM) or [[h1, .., A]]
+    (actor only); activation / seed / env_tile as Policy's.  Weights and state start at zero:
+    `load` the weights; the first `act` of a fresh policy behaves as an episode start.  Close
+    the policy before its batch."""
+
+    def __init__(self, batch_or_venv, hidden, towers, activation="tanh", seed=0, env_tile=None):
+        import torch
+        self._torch = torch
+        self.batch = getattr(batch_or_venv, "batch", batch_or_venv)
+        self.hidden = check_lstm_hidden(hidden)
+        self.towers = check_towers(towers)
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
+        self.activation = activation
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.t = 0  # sampler step counter: act(deterministic=False) without t uses and advances it
+        b = self.batch
+        p = ctypes.c_void_p()
+        with torch.cuda.device(b.device):
+            C.check(C.lib().pe_policy_create_lstm(b.handle, len(self.towers), _lstm_structs(self.hidden, len(self.towers)),
+                                                  _tower_structs(self.towers), ACTIVATIONS[activation],
+                                                  int(env_tile or 0), ctypes.byref(p)), "pe_policy_create_lstm")
+        self._p = p
+        n, A, dev = b.num_envs, self.towers[0][-1], b.device
+        self.actions = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.logits = torch.zeros((n, A), dtype=torch.float32, device=dev)
+        self.values = torch.zeros(n, dtype=torch.float32, device=dev) if len(self.towers) == 2 else None
+        self._loaded = None
+
+    @classmethod
+    def from_state_dict(cls, env, sd, activation=None, **kw):
+        """A RecurrentPolicy shaped and loaded from an sb3_contrib state dict (parse_lstm_state_dict)."""
+        hidden, towers, act, lstm, mlp = parse_lstm_state_dict(sd, activation)
+        p = cls(env, hidden, towers, act, **kw)
+        p.load((lstm, mlp))
+        return p
+
+    @property
+    def env_tile(self):
+        return int(C.lib().pe_policy_env_tile(self._handle()))
+
+    def _handle(self):
+        if not self._p:
+            raise ValueError("RecurrentPolicy is closed")
+        return self._p
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.batch._dev_index).cuda_stream
+
+    def close(self):
+        if getattr(self, "_p", None):
+            C.check(C.lib().pe_policy_destroy(self._p), "pe_policy_destroy")
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def load(self, sd_or_tensors):
+        """Repack new weights: kernels on the current stream, ordered with the forwards around
+        them.  Takes an sb3_contrib state dict or (lstm_tensors, mlp_tensors) as
+        parse_lstm_state_dict returns them; f32 contiguous tensors on the batch's device are
+        read in place, anything else is uploaded first.  The state is left as it is."""
+        torch = self._torch
+        if isinstance(sd_or_tensors, dict):
+            hidden, towers, _, lstm, mlp = parse_lstm_state_dict(sd_or_tensors)
+            if hidden != self.hidden or towers != self.towers:
+                raise ValueError(f"state dict has hidden {hidden}, towers {towers}; the policy {self.hidden}, {self.towers}")
+        else:
+            lstm, mlp = sd_or_tensors
+        _check_lstm_shapes(self.hidden, len(self.towers), lstm, self.batch.obs_dim)
+        _check_tensor_shapes(self.towers, mlp, self.hidden)
+        dev = self.batch.device
+        up = lambda x: torch.as_tensor(x).detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+        dl = [tuple(up(x) for x in tw) for tw in lstm]
+        dm = [[tuple(up(x) for x in wb) for wb in tw] for tw in mlp]
+        keep = []
+        larr = _lstm_structs(self.hidden, len(self.towers), dl, keep)
+        tarr = _tower_structs(self.towers, dm, keep)
+        with torch.cuda.device(dev):
+            C.check(C.lib().pe_policy_load_lstm(self._handle(), larr, tarr, self.batch._stream()), "pe_policy_load_lstm")
+        self._loaded = (dl, dm)  # alive until the next load (the kernels read them on the stream)
+        return self
+
+    def _flag(self, x, name):
+        torch, b = self._torch, self.batch
+        if x is None:
+            return None
+        if not (type(x) is torch.Tensor and x.is_cuda and x.get_device() == b._dev_index and x.is_contiguous()
+                and tuple(x.shape) == (b.num_envs,) and (x.dtype is torch.uint8 or x.dtype is torch.bool)):
+            raise ValueError(f"{name} must be a contiguous uint8 or bool tensor of shape {(b.num_envs,)} on {b.device}")
+        return x.data_ptr()
+
+    def act(self, obs=None, episode_start=None, deterministic=True, t=None, out=None):
+        """(actions i32 [n], logits f32 [n, A], values f32 [n] or None), device tensors; the
+        LSTM state of every env advances by one step.
+
+        obs, deterministic, t, out: as Policy.act.  episode_start: a uint8 / bool device tensor
+        [n], or a pair of them -- the step's (terminated, truncated) as they are; an env whose
+        flag (either one) is non-zero reads a zero state in this step.  None: no env starts.
+        One kernel on the current stream; no sync, no allocation: graph-capturable."""
+        torch = self._torch
+        b = self.batch
+        n, D = b.num_envs, b.obs_dim
+        if obs is None:
+            obs = b.obs
+        if not (type(obs) is torch.Tensor and obs.is_cuda and obs.get_device() == b._dev_index
+                and obs.is_contiguous() and tuple(obs.shape) == (n, D)
+                and (obs.dtype is torch.float32 or obs.dtype is torch.uint8)):
+            raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape {(n, D)} on {b.device}")
+        codes = obs.dtype is torch.uint8
+        if codes and not b.obs_codes:
+            raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
+        if isinstance(episode_start, (tuple, list)):
+            if len(episode_start) != 2:
+                raise ValueError("episode_start must be a tensor or a pair of tensors")
+            sa, sb = self._flag(episode_start[0], "episode_start[0]"), self._flag(episode_start[1], "episode_start[1]")
+        else:
+            sa, sb = self._flag(episode_start, "episode_start"), None
+        a, lg, v = out if out is not None else (self.actions, self.logits, self.values)
+        A = self.towers[0][-1]
+        for name, x, dt, shape in (("actions", a, torch.int32, (n,)), ("logits", lg, torch.float32, (n, A)),
+                                   ("values", v, torch.float32, (n,))):
+            if x is None and name != "actions":
+                continue  # an output not asked for
+            if not (type(x) is torch.Tensor and x.dtype is dt and x.is_cuda and x.get_device() == b._dev_index
+                    and x.is_contiguous() and tuple(x.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {b.device}")
+        if v is not None and len(self.towers) < 2:
+            raise ValueError("a one-tower policy has no values")
+        if deterministic:
+            mode, step = C.PE_POLICY_ARGMAX, 0
+        else:
+            mode = C.PE_POLICY_SAMPLE
+            if t is None:
+                step, self.t = self.t, self.t + 1
+            else:
+                step = int(t)
+        rc = C.lib().pe_policy_forward_lstm(self._handle(), obs.data_ptr(), int(codes), sa, sb, mode, self.seed,
+                                            step & 0xFFFFFFFF, a.data_ptr(), lg.data_ptr() if lg is not None else None,
+                                            v.data_ptr() if v is not None else None, self._stream())
+        if rc:
+            C.check(rc, "pe_policy_forward_lstm")
+        return a, lg, v
+
+    def reset_states(self):
+        """Zero the state of every env and tower (ordered on the current stream)."""
+        C.check(C.lib().pe_policy_lstm_reset_state(self._handle(), self._stream()), "pe_policy_lstm_reset_state")
+
+    def get_states(self):
+        """[(h, c), ..] per tower: fresh device tensors f32 [n, H] (SB3's lstm_states, without
+        the leading layer axis)."""
+        torch, b = self._torch, self.batch
+        out = []
+        for i in range(len(self.towers)):
+            h = torch.empty((b.num_envs, self.hidden), dtype=torch.float32, device=b.device)
+            c = torch.empty_like(h)
+            C.check(C.lib().pe_policy_lstm_get_state(self._handle(), i, h.data_ptr(), c.data_ptr(), self._stream()),
+                    "pe_policy_lstm_get_state")
+            out.append((h, c))
+        return out
+
+    def set_states(self, states):
+        """Replace the state: [(h, c), ..] per tower, [n, H] each (device tensors are read in
+        place on the current stream; anything else is uploaded first)."""
+        torch, b = self._torch, self.batch
+        if len(states) != len(self.towers):
+            raise ValueError(f"expected {len(self.towers)} (h, c) pairs")
+        dev = []
+        for h, c in states:
+            pair = tuple(torch.as_tensor(x).detach().to(device=b.device, dtype=torch.float32).contiguous() for x in (h, c))
+            if any(tuple(x.shape) != (b.num_envs, self.hidden) for x in pair):
+                raise ValueError(f"states must be [n, H] = {(b.num_envs, self.hidden)}")
+            dev.append(pair)
+        for i, (h, c) in enumerate(dev):
+            C.check(C.lib().pe_policy_lstm_set_state(self._handle(), i, h.data_ptr(), c.data_ptr(), self._stream()),
+                    "pe_policy_lstm_set_state")
+        self._states_in = dev  # alive until the next call (the kernels read them on the stream)
+
+    def host_forward(self, obs_np, states_np=None, start_np=None, tensors=None, deterministic=True, t=0):
+        """The host twin on f32 obs rows [n, D] (numpy), states [(h, c), ..] (None: zeros) and
+        start flags [n] (None: none), with the weights last loaded (or `tensors` =
+        (lstm_tensors, mlp_tensors)); env ids start at the batch's env_id_offset, the sampler
+        uses the policy's seed.  Returns ((actions, logits, values or None), new_states)."""
+        tensors = tensors if tensors is not None else self._loaded
+        if tensors is None:
+            raise ValueError("no weights loaded")
+        return lstm_host_forward(self.hidden, self.towers, tensors[0], tensors[1], self.activation, obs_np,
+                                 states=states_np, episode_start=start_np, deterministic=deterministic,
+                                 seed=self.seed, env_id_offset=int(self.batch.cfg.env_id_offset), t=t)

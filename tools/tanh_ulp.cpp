@@ -1,12 +1,14 @@
-// tanh_ulp.cpp -- worst error of pe_tanhf (and pe_expf on the sampler's range) against f64
-// libm over ALL finite f32 inputs.  Stand-alone host program:
+// tanh_ulp.cpp -- worst error of pe_tanhf and pe_sigmoidf (and pe_expf on the sampler's range)
+// against f64 libm over ALL finite f32 inputs.  Stand-alone host program:
 //
 //   clang++ -O2 -std=c++17 -ffp-contract=off -pthread -o tanh_ulp tools/tanh_ulp.cpp && ./tanh_ulp
 //
 // Prints, for pe_tanhf, tau = max |pe_tanhf(x) - tanh(x)| / (2^-24 |tanh(x)|) -- the relative
 // error in units of u = 2^-24, the figure the error bound of tests/test_policy_host.py uses --
 // with the input that reaches it, and the same figure in ulps of the f32 result; for pe_expf
-// the same over [-87, 0].  DESIGN.md section 4 records the output.
+// the same over [-87, 0]; for pe_sigmoidf the worst ABSOLUTE error against 1 / (1 + exp(-x)) --
+// the figure tests/test_policy_lstm_host.py uses (a gate's error enters the cell as an
+// absolute one) -- and the relative figures.  DESIGN.md section 4 records the output.
 #include <cmath>
 #include <cstdio>
 #include <thread>
@@ -15,8 +17,8 @@
 #include "../rl-env_amd/csrc/pe_policy_math.hpp"
 
 struct Worst {
-  double rel = 0.0, ulp = 0.0;
-  float at_rel = 0.0f, at_ulp = 0.0f;
+  double rel = 0.0, ulp = 0.0, abs = 0.0;
+  float at_rel = 0.0f, at_ulp = 0.0f, at_abs = 0.0f;
 };
 
 static double ulp_of(double exact) {
@@ -35,6 +37,7 @@ static Worst scan(uint32_t lo, uint32_t hi, F f, G ref) {  // bit patterns [lo, 
     const double got = (double)f(x), exact = ref((double)x);
     const double err = std::fabs(got - exact);
     if (err == 0.0) continue;
+    if (err > w.abs) w.abs = err, w.at_abs = x;
     const double rel = err / (std::ldexp(1.0, -24) * std::fabs(exact)), ul = err / ulp_of(exact);
     if (rel > w.rel) w.rel = rel, w.at_rel = x;
     if (ul > w.ulp) w.ulp = ul, w.at_ulp = x;
@@ -58,6 +61,7 @@ static Worst scan_all(uint32_t lo, uint64_t hi, F f, G ref) {
   for (const Worst& p : part) {
     if (p.rel > w.rel) w.rel = p.rel, w.at_rel = p.at_rel;
     if (p.ulp > w.ulp) w.ulp = p.ulp, w.at_ulp = p.at_ulp;
+    if (p.abs > w.abs) w.abs = p.abs, w.at_abs = p.at_abs;
   }
   return w;
 }
@@ -75,5 +79,15 @@ int main() {
   const Worst e = scan_all(0x80000000u, (uint64_t)pe_pol::float_to_bits(-87.0f) + 1, [](float x) { return pe_pol::pe_expf(x); },
                            [](double x) { return std::exp(x); });
   std::printf("pe_expf [-87, 0]: %.4f u at x = %.9g; %.4f ulp at x = %.9g\n", e.rel, e.at_rel, e.ulp, e.at_ulp);
+  // pe_sigmoidf over both halves (it is not odd)
+  const auto sig = [](float x) { return pe_pol::pe_sigmoidf(x); };
+  const auto sig_ref = [](double x) { return 1.0 / (1.0 + std::exp(-x)); };
+  const Worst sp = scan_all(0x00000000u, 0x7F800000ull, sig, sig_ref);
+  const Worst sn = scan_all(0x80000000u, 0xFF800000ull, sig, sig_ref);
+  std::printf("pe_sigmoidf x >= 0: abs = %.4e (%.4f u) at x = %.9g; %.4f ulp at x = %.9g\n", sp.abs,
+              sp.abs / std::ldexp(1.0, -24), sp.at_abs, sp.ulp, sp.at_ulp);
+  // (no ulp figure below 0: the result is 0 from z = -18.02 down, where sigmoid is below 2^-26)
+  std::printf("pe_sigmoidf x <  0: abs = %.4e (%.4f u) at x = %.9g\n", sn.abs, sn.abs / std::ldexp(1.0, -24),
+              sn.at_abs);
   return 0;
 }
