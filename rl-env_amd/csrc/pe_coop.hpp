@@ -887,8 +887,15 @@ __device__ __forceinline__ void pf_stage_issue(const Prefetch& pf, const State& 
     const int u = c + lane < total ? c + lane : total - 1;
     const uint64_t b = u == 0 ? rs : (u <= ng ? rg : (u <= ng + no ? ro : cg));
     const uint64_t ad = b + (u == 0 ? 0u : 16u * (uint64_t)u);
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(ad),
-                                     (__attribute__((address_space(3))) void*)(lds + 4 * c), 16, 0, 0);
+    // Lanes past the last unit issue nothing: an LDS-DMA lane writes LDS unit c + lane whatever
+    // address it loads from, and the units after the record are not this wave's -- the info
+    // wave's register-staged rows start at unit `total` (pe_step_quad info_reg), and a clamped
+    // tail lane's copy of the last unit, landing after that wave's write, replaced their first
+    // rows (64x64/C64: units 119..127, six grid rows missing from the terminal info's plant
+    // counts; tests/test_gpu_termination.py S5 with prefetch_every = 1)
+    if (c + lane < total)
+      __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(ad),
+                                       (__attribute__((address_space(3))) void*)(lds + 4 * c), 16, 0, 0);
   }
 }
 

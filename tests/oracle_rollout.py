@@ -12,10 +12,14 @@ def scal_from_fixture(scal6, n):
 
 class OracleVec:
     """Device-rng (Philox) DummyVecEnv-style rollout of selected global env ids,
-    mirroring pe_create (all envs reset with episode 0) + pe_step(autoreset)."""
+    mirroring pe_create (all envs reset with episode 0) + pe_step(autoreset).
+    rules: po_config overrides (thirsty_plant_prob and the eight r_* rewards)."""
 
-    def __init__(self, cfg_tuple, env_ids, seed, max_steps=1000, map_algo=0):
-        self.cfg = O.config(*cfg_tuple, max_steps=max_steps, map_algo=map_algo)
+    def __init__(self, cfg_tuple, env_ids, seed, max_steps=1000, map_algo=0, **rules):
+        bad = [k for k in rules if k != "thirsty_plant_prob" and not k.startswith("r_")]
+        if bad:
+            raise TypeError(f"unknown rules: {bad}")
+        self.cfg = O.config(*cfg_tuple, max_steps=max_steps, map_algo=map_algo, **rules)
         self.ids = np.asarray(env_ids, np.int64)
         self.seed = seed
         self.b = O.Batch(self.cfg, len(self.ids))
@@ -47,7 +51,7 @@ class OracleBatch:
     lets the host-side vec-env logic run and be checked without a GPU)."""
 
     def __init__(self, n, grid_size, num_plants, num_obstacles, lidar_range, lidar_channels, seed=0,
-                 max_steps=1000, obs_codes=False):
+                 max_steps=1000, obs_codes=False, **rules):
         import torch
         self.torch = torch
         self.obs_codes = bool(obs_codes)  # io holds byte codes (plantos_amd/codes.py), as PlantOSBatch's
@@ -55,7 +59,7 @@ class OracleBatch:
         self.num_envs = n
         self.grid_size = grid_size
         self.cfg_t = (grid_size, num_plants, num_obstacles, lidar_range, lidar_channels)
-        self.ov = OracleVec(self.cfg_t, np.arange(n), seed, max_steps=max_steps)
+        self.ov = OracleVec(self.cfg_t, np.arange(n), seed, max_steps=max_steps, **rules)
         self.obs_dim = O.obs_dim(self.ov.cfg)
         D = self.obs_dim
         self.obs = torch.as_tensor(self.ov.obs())

@@ -129,6 +129,52 @@ def test_rng_state_round_trip():
     b.close()
 
 
+@pytest.mark.parametrize("cfgt", [(20, 10, 12, 6, 16), (7, 3, 3, 3, 12)], ids=["g20", "g7"])
+def test_search_under_non_default_rules(cfgt):
+    """The search's own copy of the reward code and of the truncation test (pe_mcts.hip) under
+    the `adv` rewards and max_steps = 30: a third of the envs start at step 25 or later, so
+    every rollout of theirs truncates; another third start one move from a finished map
+    (rules_util.inject_last_cell), so the search meets termination and r_complete.  Every env
+    against the oracle: action, root order, root visits, f64 value sums, the stream afterwards."""
+    import rules_util as U
+    from plantos_amd.mcts import MCTS
+    n, max_steps, n_sims, depth, seed = 70, 30, 20, 40, 41
+    rules = U.PRESETS["adv"]
+    tw = U.Twin(cfgt, n, 8, max_steps, 0.25, rules)
+    b = U.make_batch(cfgt, n, 8, max_steps, 0.25, rules)
+    acts = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    for t in range(6):  # off the reset states
+        b.synth_actions(U.ASEED, t, out=acts)
+        tw.step(np_(acts))
+        b.step(acts)
+    before = U.snapshot(tw.ov)
+    late, inj = np.arange(0, n, 3), np.arange(1, n, 3)
+    tw.ov.b.scal[late, O.S_STEP] = 25 + late % 5
+    U.inject_last_cell(tw.ov, inj)
+    U.push(tw.ov, b, before)
+    m = MCTS(b, n_simulations=n_sims, max_depth=depth, seed=seed)
+    a, order, cv, cval = m.search(root_stats=True)
+    torch.cuda.synchronize()
+    a, order, cv, cval = np_(a), np_(order), np_(cv), np_(cval)
+    key, pos = m.get_rng_state()
+    ob = tw.ov.b
+    best = np.zeros(n)
+    for e in range(n):
+        r = O.NpMT(seed + e)
+        oa, oo, ocv, ocval = O.mcts_search(tw.ov.cfg, ob.cells[e], ob.visits[e], ob.explored[e], ob.scal[e], r,
+                                           n_sims, 1.414, depth)
+        assert oa == a[e] and (oo == order[e]).all() and (ocv == cv[e]).all(), e
+        assert (ocval == cval[e]).all(), (e, ocval, cval[e])  # f64 sums, bit-exact
+        assert same_stream(key[e], pos[e], *r.state()), e
+        best[e] = ocval.max()
+    # the inputs did their work: the one-move-from-done envs saw r_complete (33.301) in a value
+    # sum; a late env's rollouts are at most 5 steps of at most 0.69 each
+    assert (best[inj] > 33.0).all() and (best[late] < 20 * 5 * 0.7).all()
+    U.compare_state(b, tw.ov, "search left the state alone")
+    m.close()
+    b.close()
+
+
 def test_headline_size_search():
     """65536 envs, train_mcts settings (n_sims 50, max_depth 100): properties on
     every env, the oracle on a sample."""

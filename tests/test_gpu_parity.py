@@ -111,9 +111,25 @@ def test_dummyvecenv_trajectory_gpu(name):
     """Reference DummyVecEnv rollouts; reset layouts supplied from the fixture
     (CPython-stream mode), everything else computed on the GPU."""
     f = load(name)
+    _replay_trajectory_gpu(f, make(cfg_tuple(f), f["actions"].shape[1]))
+
+
+def test_dummyvecenv_trajectory_gpu_non_default_rules():
+    """The reference's own rollout under non-default rules (thirsty_plant_prob = 0.5, the `adv`
+    rewards; 8 terminations with the bonus, every reachable reward value -- see
+    test_oracle_golden) replayed on the GPU with PlantOSBatch(rewards=, thirsty_plant_prob=)."""
+    from test_oracle_golden import fixture_rules
+    f = load("traj_g12r2_rules")
+    rules = fixture_rules(f)
+    p = rules.pop("thirsty_plant_prob")
+    b = make(cfg_tuple(f), f["actions"].shape[1], rewards=rules, thirsty_plant_prob=p)
+    assert b.kernel_name == KERNELS["g12r2"]
+    _replay_trajectory_gpu(f, b)
+
+
+def _replay_trajectory_gpu(f, b):
     acts = f["actions"]
     T, N = acts.shape
-    b = make(cfg_tuple(f), N)
     obs0 = np_(b.load_maps(np.arange(N), f["maps0"], f["rover0"]))
     assert (obs0 == f["obs0"]).all()
     ri = 0

@@ -110,7 +110,33 @@ def test_dummyvecenv_trajectories(name):
     """N envs sharing one global `random` stream, DummyVecEnv auto-reset order
     (A2C_training.py:216-218): terminal obs, reset obs, rewards, flags."""
     f = load(name)
-    c = O.config(*cfg_tuple(f))
+    _replay_trajectory(f, O.config(*cfg_tuple(f)))
+
+
+def fixture_rules(f):
+    """po_config overrides of a fixture recorded under non-default rules (tools/gen_golden.py
+    gen_traj_rules): `rewards` in the r_* order of po_config, `thirsty_plant_prob`"""
+    keys = [k for k, _ in O.POConfig._fields_ if k.startswith("r_")]
+    assert len(keys) == len(f["rewards"]) == 8
+    return dict(zip(keys, (float(v) for v in f["rewards"])), thirsty_plant_prob=float(f["thirsty_plant_prob"]))
+
+
+def test_dummyvecenv_trajectory_non_default_rules():
+    """The checker itself under non-default rules: the reference's fork env with
+    thirsty_plant_prob = 0.5 and the `adv` rewards (rules_util.py), 4 envs x 500 steps with an
+    explorer that waters -- 8 terminations and all seven reachable reward values, -1.11, -0.91,
+    -0.31, -0.08, 0.29, 0.69 and 33.591 (asserted here and by the generator).  Rewards as f64."""
+    from rules_util import PRESETS
+    f = load("traj_g12r2_rules")
+    rules = fixture_rules(f)
+    assert {k: v for k, v in rules.items() if k.startswith("r_")} == PRESETS["adv"] and rules["thirsty_plant_prob"] == 0.5
+    assert cfg_tuple(f) == (12, 4, 6, 2, 10) and f["actions"].shape == (500, 4) and int(f["seed"]) == 7
+    assert int(f["terminated"].sum()) == 8
+    assert sorted(set(np.round(f["reward"], 9).ravel().tolist())) == [-1.11, -0.91, -0.31, -0.08, 0.29, 0.69, 33.591]
+    _replay_trajectory(f, O.config(*cfg_tuple(f), **rules))
+
+
+def _replay_trajectory(f, c):
     acts = f["actions"]
     T, N = acts.shape
     mt = O.MT(int(f["seed"]))

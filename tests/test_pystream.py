@@ -48,6 +48,26 @@ def test_dummyvecenv_reset_order(name):
     assert s.getrandbits32() == int(f["next_u32"])
 
 
+def test_reset_order_with_non_default_thirsty_prob():
+    """thirsty_plant_prob = 0.5 on the host path (pe_pystream.cpp): the reference's fork env
+    built with it (tests/golden/traj_g12r2_rules.npz) -- maps0, then every auto-reset map."""
+    f = load("traj_g12r2_rules")
+    G, P, O, R, C = cfg_tuple(f)
+    p = float(f["thirsty_plant_prob"])
+    assert p == 0.5
+    s = PyStream(G, P, O, int(f["seed"]), thirsty_plant_prob=p)
+    cells, rover = s.next(f["maps0"].shape[0])
+    assert (cells == f["maps0"]).all() and (rover == f["rover0"]).all()
+    k = len(f["reset_t"])
+    assert k >= 8
+    cells, rover = s.next(k)
+    assert (cells == f["reset_cells"]).all() and (rover == f["reset_rover"]).all()
+    assert s.getrandbits32() == int(f["next_u32"])
+    # the maps tell 0.5 from the default: the default stream draws other plants thirsty
+    d = PyStream(G, P, O, int(f["seed"]))
+    assert (d.next(f["maps0"].shape[0])[0] != f["maps0"]).any()
+
+
 def test_no_room_is_value_error():
     s = PyStream(5, 22, 3, 0)
     with pytest.raises(ValueError):

@@ -18,6 +18,8 @@ Fixtures written (all under tests/golden/):
                          gradio-app/plantos_env_new.py:162-245) incl. pre-step obs
   traj_<cfg>.npz         DummyVecEnv-style multi-env rollouts with auto-reset
                          (A2C_training.py:216-218 semantics, SB3 step_wait)
+  traj_g12r2_rules.npz   the same under non-default rewards and thirsty_plant_prob
+                         (`python tools/gen_golden.py rules`)
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py
 """
@@ -399,6 +401,78 @@ def gen_traj(cfg, n_envs, steps, seed, policy):
     print(f"traj_{cfg}_{policy}: {n_envs}x{steps}, resets={len(reset_maps)}, term={int(te.sum())}")
 
 
+# the `adv` reward preset of tests/rules_util.py (12 distinct float32 step rewards)
+ADV_REWARDS = dict(R_GOAL=0.7, R_MISTAKE=-0.3, R_INVALID=-1.1, R_WATER_EMPTY=-0.9, R_STEP=-0.01,
+                   R_EXPLORATION=0.3, R_REVISIT=-0.07, R_COMPLETE_EXPLORATION=33.301)
+
+
+def gen_traj_rules():
+    """tests/golden/traj_g12r2_rules.npz: gen_traj's DummyVecEnv rollout of the fork env under
+    NON-DEFAULT rules -- 12x12, 4 plants, 6 obstacles, R 2, C 10, thirsty_plant_prob = 0.5, the
+    eight reward attributes set to ADV_REWARDS after construction; 4 envs, 500 steps, seed 7;
+    the explorer policy at 0.8 plus "on a plant, water with probability 0.5".  gen_traj's
+    arrays plus `rewards` (8 f64, the oracle's r_* order) and `thirsty_plant_prob`."""
+    cfgt, n_envs, steps, seed, p = (12, 4, 6, 2, 10), 4, 500, 7, 0.5
+    G, P, Ob, R, C = cfgt
+    envs = []
+    for _ in range(n_envs):
+        e = ForkEnv(grid_size=G, num_plants=P, num_obstacles=Ob, lidar_range=R, lidar_channels=C,
+                    thirsty_plant_prob=p, map_generation_algo="original")
+        for k, v in ADV_REWARDS.items():
+            assert hasattr(e, k)
+            setattr(e, k, v)
+        envs.append(e)
+    random.seed(seed)
+    rng = np.random.default_rng(seed + 1000)
+    obs0 = np.array([e.reset()[0] for e in envs], np.float32)
+    maps0 = np.array([cells_of(e) for e in envs], np.uint8)
+    rov0 = np.array([e.rover_pos for e in envs], np.int32)
+    D = obs0.shape[1]
+    acts = np.zeros((steps, n_envs), np.int32)
+    obs = np.zeros((steps, n_envs, D), np.float32)
+    term_obs = np.zeros((steps, n_envs, D), np.float32)
+    rew = np.zeros((steps, n_envs), np.float64)
+    te = np.zeros((steps, n_envs), np.uint8)
+    tr = np.zeros((steps, n_envs), np.uint8)
+    reset_maps = []
+    for t in range(steps):
+        for i, e in enumerate(envs):
+            a = bfs_action(e) if rng.random() < 0.8 else int(rng.integers(0, 5))
+            if e.rover_pos in e.plants and rng.random() < 0.5:
+                a = 4
+            acts[t, i] = a
+            o, r, a_te, a_tr, _ = e.step(a)
+            rew[t, i] = r
+            te[t, i] = a_te
+            tr[t, i] = a_tr
+            if a_te or a_tr:
+                term_obs[t, i] = o
+                o, _ = e.reset()
+                reset_maps.append((t, i, cells_of(e), e.rover_pos))
+            obs[t, i] = o
+    # what the fixture is for: terminations (the r_complete bonus) and every reachable reward
+    assert int(te.sum()) >= 8, int(te.sum())
+    seen = sorted(set(np.round(rew, 9).ravel().tolist()))
+    assert seen == [-1.11, -0.91, -0.31, -0.08, 0.29, 0.69, 33.591], seen
+    path = os.path.join(OUT, "traj_g12r2_rules.npz")
+    np.savez_compressed(
+        path, config=np.array(cfgt, np.int32),
+        seed=np.int64(seed), maps0=maps0, rover0=rov0, obs0=obs0, actions=acts, obs=obs,
+        terminal_obs=term_obs, reward=rew, terminated=te, truncated=tr,
+        reset_t=np.array([m[0] for m in reset_maps], np.int32),
+        reset_env=np.array([m[1] for m in reset_maps], np.int32),
+        reset_cells=np.array([m[2] for m in reset_maps], np.uint8).reshape(-1, G, G),
+        reset_rover=np.array([m[3] for m in reset_maps], np.int32).reshape(-1, 2),
+        next_u32=np.int64(random.getrandbits(32)),
+        rewards=np.array([ADV_REWARDS[k] for k in ("R_GOAL", "R_MISTAKE", "R_INVALID", "R_WATER_EMPTY", "R_STEP",
+                                                   "R_EXPLORATION", "R_REVISIT", "R_COMPLETE_EXPLORATION")],
+                         np.float64),
+        thirsty_plant_prob=np.float64(p))
+    assert os.path.getsize(path) < 300 * 1024, os.path.getsize(path)
+    print(f"traj_g12r2_rules: {n_envs}x{steps}, resets={len(reset_maps)}, term={int(te.sum())}, "
+          f"{os.path.getsize(path)} bytes")
+
+
 def load_curriculum_wrapper(source="A2C_training.py"):
     """The reference's own CurriculumWrapper class (A2C_training.py:37-109, or the
     trainingCode.py:24-98 variant), compiled from the reference file: only that class
@@ -670,5 +744,8 @@ if __name__ == "__main__":
         main_mcts()
     elif sys.argv[1:] == ["maze"]:
         main_maze()
+    elif sys.argv[1:] == ["rules"]:
+        os.makedirs(OUT, exist_ok=True)
+        gen_traj_rules()
     else:
         main()
