@@ -24,16 +24,23 @@ SRC_RENDER = os.path.join(HERE, "csrc", "pe_render.hip")
 SRC_POLICY = os.path.join(HERE, "csrc", "pe_policy.hip")
 SRC_POLICY_HOST = os.path.join(HERE, "csrc", "pe_policy_host.cpp")
 SRC_POLICY_LSTM = os.path.join(HERE, "csrc", "pe_policy_lstm.hip")
-SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST, SRC_POLICY_LSTM]
+SRC_ROLLOUT = os.path.join(HERE, "csrc", "pe_rollout.hip")
+SRC_ROLLOUT_HOST = os.path.join(HERE, "csrc", "pe_rollout_host.cpp")
+SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST, SRC_POLICY_LSTM, SRC_ROLLOUT,
+           SRC_ROLLOUT_HOST]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in
                   ("pe_device.hpp", "pe_fast.hpp", "pe_quad.hpp", "pe_coop.hpp", "pe_handle.hpp", "pe_far.hpp",
-                   "pe_policy_math.hpp", "pe_policy_impl.hpp")] + [
+                   "pe_policy_math.hpp", "pe_policy_impl.hpp", "pe_rollout_math.hpp")] + [
     os.path.join(REPO, "include", "plantos_batch.h"), os.path.join(HERE, "tools_gen_lidar.py")]
 OUT = os.path.join(HERE, "plantos_amd", "libplantos_hip.so")
 OBJ_DIR = os.path.join(REPO, "build", "obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
           "-Wno-unused-function", "-Wno-unused-variable"]
+# Flags of single sources.  pe_rollout.hip: the SLP vectoriser packs two multiplies of the GAE
+# chain into one v_pk_mul_f32 whose unused half is a register of the window still being
+# loaded, and the wait that costs serialises the scan with the loads it should overlap.
+SOURCE_FLAGS = {SRC_ROLLOUT: ["-fno-slp-vectorize"]}
 
 
 def build(force=False, verbose=False, out=OUT, extra_flags=(), obj_dir=None):
@@ -55,7 +62,7 @@ def build(force=False, verbose=False, out=OUT, extra_flags=(), obj_dir=None):
     objs, procs = [], []
     for src in SOURCES:
         obj = os.path.join(obj_dir, os.path.basename(src) + ".o")
-        cmd = [HIPCC] + CFLAGS + list(extra_flags) + ["-c", "-o", obj, src]
+        cmd = [HIPCC] + CFLAGS + SOURCE_FLAGS.get(src, []) + list(extra_flags) + ["-c", "-o", obj, src]
         if verbose:
             print(" ".join(cmd))
         procs.append((subprocess.Popen(cmd), cmd))

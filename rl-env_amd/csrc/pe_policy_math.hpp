@@ -89,6 +89,42 @@ PE_HD float pe_tanhf(float x) {
   return bits_to_float(float_to_bits(y) | sign);
 }
 
+// log(x) in f32 (the log-probabilities of the rollout, pe_rollout_math.hpp).  x = 2^k m with m
+// in [sqrt(1/2), sqrt(2)) taken from the bits; f = m - 1 (exact), s = f / (2 + f),
+// log(m) = f - f^2/2 + s (f^2/2 + R(s^2)), R the even / odd split polynomial in s^2 with the
+// coefficients Lg1 .. Lg4 of fdlibm's logf, in fmaf; the result is assembled as
+// k ln2_hi - ((f^2/2 - (s (f^2/2 + R) + k ln2_lo)) - f), ln2 split hi + lo.
+// Domain: positive normal floats.  Outside it: NaN passes through; +-0 -> -inf; x < 0
+// (-inf included) -> the quiet NaN 0x7FC00000; +inf -> +inf; a positive subnormal is scaled
+// by 2^23 (exact) first and gets its own logarithm.
+PE_HD float pe_logf(float x) {
+#pragma clang fp contract(off)
+  if (x != x) return x;
+  uint32_t ix = float_to_bits(x);
+  if ((ix & 0x7FFFFFFFu) == 0u) return bits_to_float(0xFF800000u);
+  if (ix & 0x80000000u) return bits_to_float(0x7FC00000u);
+  if (ix == 0x7F800000u) return x;
+  int32_t k = 0;
+  if (ix < 0x00800000u) {
+    ix = float_to_bits(x * 8388608.0f);  // 2^23: exact
+    k = -23;
+  }
+  ix += 0x3F800000u - 0x3F3504F3u;
+  k += (int32_t)(ix >> 23) - 127;
+  ix = (ix & 0x007FFFFFu) + 0x3F3504F3u;
+  const float f = bits_to_float(ix) - 1.0f;
+  const float s = f / (2.0f + f);
+  const float z = s * s;
+  const float w = z * z;
+  const float t1 = w * fmaf(w, 0.24279078841f, 0.40000972152f);    // Lg4, Lg2
+  const float t2 = z * fmaf(w, 0.28498786688f, 0.66666662693f);    // Lg3, Lg1
+  const float R = t2 + t1;
+  const float hfsq = (0.5f * f) * f;
+  const float dk = (float)k;
+  const float lo = fmaf(s, hfsq + R, dk * 9.0580006145e-06f);      // ln2 lo
+  return fmaf(dk, 6.9313812256e-01f, -((hfsq - lo) - f));          // ln2 hi: dk * hi is exact
+}
+
 PE_HD float pe_relu(float z) { return z > 0.0f ? z : 0.0f; }
 
 // sigmoid(z) = 1/2 + 1/2 tanh(z / 2): no division of its own, results 0, 1 or in
@@ -159,6 +195,22 @@ PE_HD int policy_sample(const float* l, int A, float u) {
     if (us < cum) return a;
   }
   return A - 1;
+}
+
+// log-probability of action a under the sampler's distribution: z_k = l_k - max l,
+// S = the f32 sum of pe_expf(z_k) in action order (policy_sample's S, in [1, 8]),
+// z_a - pe_logf(S).
+PE_HD float policy_logprob(const float* l, int A, int a) {
+#pragma clang fp contract(off)
+  float m = l[0];
+  for (int k = 1; k < A; ++k) m = l[k] > m ? l[k] : m;
+  float S = 0.0f, za = 0.0f;
+  for (int k = 0; k < A; ++k) {
+    const float z = l[k] - m;
+    S = S + pe_expf(z);
+    za = k == a ? z : za;
+  }
+  return za - pe_logf(S);
 }
 
 }  // namespace pe_pol

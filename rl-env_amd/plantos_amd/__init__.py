@@ -6,9 +6,13 @@ Public surface:
   PlantOSVectorEnv  gymnasium-0.29 VectorEnv convention over the same batch
   Policy            batched MLP policy inference on the device: obs (codes or f32) -> actions
   RecurrentPolicy   the same for LSTM policies (sb3_contrib MlpLstmPolicy), state on the device
+  RolloutCollector  on-policy rollouts on the device: rollout buffer, log-probs, time-limit
+                    bootstrap and GAE (SB3's collect_rollouts); returns a Rollout
 """
 from .batch import PlantOSBatch  # noqa: F401
 from .policy import Policy, RecurrentPolicy  # noqa: F401
+from .rollout import Rollout, RolloutCollector  # noqa: F401
 from .vec_env import PlantOSVecEnv, PlantOSVectorEnv  # noqa: F401
 
-__all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy"]
+__all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy", "Rollout",
+           "RolloutCollector"]

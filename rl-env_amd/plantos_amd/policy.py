@@ -167,11 +167,14 @@ def host_forward(towers, tensors, activation, obs, deterministic=True, seed=0, e
 
 
 def math_host(which, x):
-    """pe_tanhf ("tanh"), pe_expf ("exp") or pe_sigmoidf ("sigmoid") of a float32 array, as the
-    twins and the kernels compute them."""
+    """pe_tanhf ("tanh"), pe_expf ("exp"), pe_sigmoidf ("sigmoid") or pe_logf ("log") of a float32
+    array, as the twins and the kernels compute them."""
     x = np.ascontiguousarray(x, np.float32)
     y = np.empty_like(x)
     P = ctypes.c_void_p
+    if which == "log":  # (a function of its own: pe_policy_math_host's selectors stay 0..2)
+        C.check(C.lib().pe_logf_host(x.size, x.ctypes.data_as(P), y.ctypes.data_as(P)), "pe_logf_host")
+        return y
     C.check(C.lib().pe_policy_math_host({"tanh": 0, "exp": 1, "sigmoid": 2}[which], x.size, x.ctypes.data_as(P),
                                         y.ctypes.data_as(P)), "pe_policy_math_host")
     return y

@@ -1,0 +1,321 @@
+"""RolloutCollector: on-policy rollouts collected on the device.
+
+What Stable-Baselines3's OnPolicyAlgorithm.collect_rollouts and
+RolloutBuffer.compute_returns_and_advantage add to the act / step loop (A2C(n_steps=5,
+gamma=0.99, gae_lambda=1.0), A2C_training.py:229-247; the PPO family with n_steps=1024,
+gae_lambda=0.95, trainingCode.py:140-162): per-step storage of obs, actions, rewards, episode
+starts, values and log-probs, the time-limit bootstrap of truncated episodes and the
+reverse-time GAE scan -- the C-ABI's pe_rollout_record / pe_rollout_gae
+(include/plantos_batch.h, "Rollout collection") around Policy.act and PlantOSBatch.step.
+Learners stay out of scope: the Rollout is the data they consume.
+
+    collector = RolloutCollector(venv, policy, n_steps=5, gamma=0.99, gae_lambda=1.0)
+    venv.reset()
+    while training:
+        ro = collector.collect()            # device tensors; no host sync
+        learner.update(ro.obs_f32(), ro.actions, ro.advantages, ro.returns, ro.log_probs, ro.values)
+        policy.load(learner.state_dict())
+
+Every output is defined bit for bit by the host twins (`host_record`, `host_gae`,
+`RolloutCollector.host_rollout`), which need no device.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _capi as C
+from .policy import Policy, RecurrentPolicy
+
+ROW_ALIGN = 512  # bytes: every row of the buffer starts as aligned as a fresh torch allocation
+
+
+def _p(x):
+    if x is None:
+        return None
+    return ctypes.c_void_p(x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())
+
+
+def host_record(logits, actions, reward, terminated, truncated, gamma, terminal_value=None, episode_return=None,
+                episode_length=None, ep_count=None, ep_return_sum=None, ep_length_sum=None):
+    """The record step on numpy arrays (pe_rollout_record_host): returns (log_prob f32[n],
+    reward f32[n], start_next u8[n]); the accumulators given (i32 / f64 / i32 [n], contiguous)
+    are updated in place.  terminal_value None: no bootstrap."""
+    logits = np.ascontiguousarray(logits, np.float32)
+    n, A = logits.shape
+    actions = np.ascontiguousarray(actions, np.int32)
+    reward = np.ascontiguousarray(reward, np.float32)
+    te = np.ascontiguousarray(np.asarray(terminated) != 0, np.uint8)
+    tr = np.ascontiguousarray(np.asarray(truncated) != 0, np.uint8)
+    tv = None if terminal_value is None else np.ascontiguousarray(terminal_value, np.float32)
+    er = None if episode_return is None else np.ascontiguousarray(episode_return, np.float64)
+    el = None if episode_length is None else np.ascontiguousarray(episode_length, np.int32)
+    for x, dt in ((ep_count, np.int32), (ep_return_sum, np.float64), (ep_length_sum, np.int32)):
+        if x is not None and not (isinstance(x, np.ndarray) and x.dtype == dt and x.flags.c_contiguous and x.shape == (n,)):
+            raise ValueError(f"accumulators must be contiguous numpy arrays of shape {(n,)} (i32, f64, i32)")
+    for x in (actions, reward, te, tr, tv, er, el):
+        if x is not None and x.shape != (n,):
+            raise ValueError(f"per-env inputs must have shape {(n,)}")
+    lp = np.zeros(n, np.float32)
+    ro = np.zeros(n, np.float32)
+    st = np.zeros(n, np.uint8)
+    C.check(C.lib().pe_rollout_record_host(n, A, _p(logits), _p(actions), _p(reward), _p(te), _p(tr), _p(tv), _p(er),
+                                           _p(el), float(gamma), _p(lp), _p(ro), _p(st), _p(ep_count),
+                                           _p(ep_return_sum), _p(ep_length_sum)), "pe_rollout_record_host")
+    return lp, ro, st
+
+
+def host_gae(rewards, values, starts, last_values, gamma, gae_lambda):
+    """The GAE scan on numpy arrays (pe_rollout_gae_host): rewards / values f32 [T, n], starts
+    u8 [T + 1, n] (row T: the last step's done flags), last_values f32 [n]; returns
+    (advantages, returns) f32 [T, n]."""
+    rewards = np.ascontiguousarray(rewards, np.float32)
+    values = np.ascontiguousarray(values, np.float32)
+    starts = np.ascontiguousarray(np.asarray(starts) != 0, np.uint8)
+    last_values = np.ascontiguousarray(last_values, np.float32)
+    if rewards.ndim != 2:
+        raise ValueError("rewards must be [T, n]")
+    T, n = rewards.shape
+    if values.shape != (T, n) or starts.shape != (T + 1, n) or last_values.shape != (n,):
+        raise ValueError(f"expected values {(T, n)}, starts {(T + 1, n)}, last_values {(n,)}")
+    adv = np.zeros((T, n), np.float32)
+    ret = np.zeros((T, n), np.float32)
+    C.check(C.lib().pe_rollout_gae_host(T, n, n, n, n, n, _p(rewards), _p(values), _p(starts), _p(last_values),
+                                        float(gamma), float(gae_lambda), _p(adv), _p(ret)), "pe_rollout_gae_host")
+    return adv, ret
+
+
+def record_device(logits, actions, reward, terminated, truncated, gamma, log_prob, reward_out, start_next,
+                  terminal_value=None, episode_return=None, episode_length=None, ep_count=None, ep_return_sum=None,
+                  ep_length_sum=None):
+    """pe_rollout_record on device tensors (contiguous, all on logits' device), on torch's
+    current stream.  reward_out may be `reward`."""
+    import torch
+    n, A = logits.shape
+    with torch.cuda.device(logits.device):
+        C.check(C.lib().pe_rollout_record(
+            n, A, _p(logits), _p(actions), _p(reward), _p(terminated), _p(truncated), _p(terminal_value),
+            _p(episode_return), _p(episode_length), float(gamma), _p(log_prob), _p(reward_out), _p(start_next),
+            _p(ep_count), _p(ep_return_sum), _p(ep_length_sum),
+            ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)), "pe_rollout_record")
+
+
+def gae_device(rewards, values, starts, last_values, gamma, gae_lambda, advantages, returns):
+    """pe_rollout_gae on device tensors, on torch's current stream: rewards / values /
+    advantages / returns f32 [T, n] and starts u8 [T + 1, n], each with unit stride over envs
+    and any row stride (advantages and returns the same one); last_values f32 [n]."""
+    import torch
+    T, n = rewards.shape
+    for name, x, rows in (("rewards", rewards, T), ("values", values, T), ("starts", starts, T + 1),
+                          ("advantages", advantages, T), ("returns", returns, T)):
+        if tuple(x.shape) != (rows, n) or (n > 1 and x.stride(1) != 1):
+            raise ValueError(f"{name} must be [{rows}, {n}] with unit stride over envs")
+    if T > 1 and advantages.stride(0) != returns.stride(0):
+        raise ValueError("advantages and returns must share their row stride")
+    rs = lambda x: x.stride(0) if x.shape[0] > 1 else n  # noqa: E731
+    with torch.cuda.device(rewards.device):
+        C.check(C.lib().pe_rollout_gae(T, n, rs(rewards), rs(values), starts.stride(0), rs(advantages), _p(rewards),
+                                       _p(values), _p(starts), _p(last_values), float(gamma), float(gae_lambda),
+                                       _p(advantages), _p(returns),
+                                       ctypes.c_void_p(torch.cuda.current_stream(rewards.device).cuda_stream)),
+                "pe_rollout_gae")
+
+
+class Rollout:
+    """One collect()'s data: device tensors, most of them views of the collector's storage
+    (the next collect() overwrites them).
+
+    obs [T, n, D] (uint8 codes on an ``obs_codes`` batch, else float32; rows strided),
+    actions i32 [T, n], rewards f32 [T, n] (strided; with the time-limit bootstrap added
+    where it applies), episode_starts u8 [T, n] (strided), values, log_probs, advantages,
+    returns f32 [T, n], last_values f32 [n], last_dones u8 [n], and the per-env episode
+    accumulators since the collector was made: ep_count i32 [n], ep_return_sum f64 [n],
+    ep_length_sum i32 [n]."""
+
+    FIELDS = ("obs", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns",
+              "last_values", "last_dones", "ep_count", "ep_return_sum", "ep_length_sum")
+
+    def __init__(self, collector, **fields):
+        self._c = collector
+        for k in self.FIELDS:
+            setattr(self, k, fields[k])
+
+    def obs_f32(self, out=None):
+        """The obs as float32 [T * n, D] (step-major).  On an ``obs_codes`` batch: one
+        pe_expand_obs_codes launch over the T rows into `out` (or a new tensor).  On a
+        float32 batch: a view of the storage where the rows allow one, else one strided copy."""
+        return self._c._obs_f32(out)
+
+
+class RolloutCollector:
+    """Collects `n_steps` steps of every env of a PlantOSBatch (or a PlantOSVecEnv's batch) under
+    a two-tower Policy, entirely on the device.
+
+    gamma / gae_lambda: the GAE parameters; bootstrap_timeouts: add gamma * V(terminal obs) to
+    the reward of an episode cut by the time limit only (SB3's TimeLimit.truncated handling);
+    deterministic: argmax actions instead of the policy's Philox sampler (whose step counter
+    advances by one per step, across collects).  Storage is allocated here, once.  ValueError
+    for a one-tower policy (no values), a RecurrentPolicy, n_steps < 1, a policy of another
+    batch, or a batch without autoreset."""
+
+    def __init__(self, batch_or_venv, policy, n_steps, gamma=0.99, gae_lambda=0.95, bootstrap_timeouts=True,
+                 deterministic=False):
+        import torch
+        self._torch = torch
+        b = self.batch = getattr(batch_or_venv, "batch", batch_or_venv)
+        if isinstance(policy, RecurrentPolicy):
+            raise ValueError("recurrent rollouts are not supported: the bootstrap needs a value forward that does not "
+                             "advance the LSTM state")
+        if not isinstance(policy, Policy):
+            raise ValueError("policy must be a plantos_amd.Policy")
+        if len(policy.towers) != 2:
+            raise ValueError("a rollout needs values: the policy must have a value tower")
+        if policy.batch is not b:
+            raise ValueError("the policy was made for another batch")
+        if int(n_steps) < 1:
+            raise ValueError(f"n_steps must be >= 1, got {n_steps}")
+        b.handle  # a closed batch raises here
+        policy._handle()
+        if not b.cfg.autoreset:
+            raise ValueError("a rollout needs a batch with autoreset=True")
+        self.policy = policy
+        self.n_steps = T = int(n_steps)
+        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
+        self.bootstrap_timeouts, self.deterministic = bool(bootstrap_timeouts), bool(deterministic)
+        n, D, A, dev = b.num_envs, b.obs_dim, policy.towers[0][-1], b.device
+        io_b = b.io_bytes()
+        ro = b._io_offsets()[0]
+        # a row: the step's io buffer | start u8 [n] | padding
+        self._so = io_b
+        self._stride = stride = (io_b + n + ROW_ALIGN - 1) // ROW_ALIGN * ROW_ALIGN
+        self._buf = torch.zeros((T + 1) * stride, dtype=torch.uint8, device=dev)
+        self._rows = [self._buf[t * stride:t * stride + io_b] for t in range(T + 1)]
+        self._row_views = [b.io_views(r) for r in self._rows]
+        self._start = [self._buf[t * stride + io_b:t * stride + io_b + n] for t in range(T + 1)]
+        m = self._buf.view(T + 1, stride)
+        f32, i32 = torch.float32, torch.int32
+        if b.obs_codes:
+            self._obs = m[:T, :n * D].unflatten(1, (n, D))
+        else:
+            self._obs = m[:T, :4 * n * D].view(f32).unflatten(1, (n, D))
+        self._rewards = m[1:, ro:ro + 4 * n].view(f32)
+        self._starts_all = m[:, io_b:io_b + n]
+        self.actions = torch.zeros((T, n), dtype=i32, device=dev)
+        self.values = torch.zeros((T, n), dtype=f32, device=dev)
+        self.log_probs = torch.zeros((T, n), dtype=f32, device=dev)
+        self.advantages = torch.zeros((T, n), dtype=f32, device=dev)
+        self.returns = torch.zeros((T, n), dtype=f32, device=dev)
+        self.last_values = torch.zeros(n, dtype=f32, device=dev)
+        self.terminal_values = torch.zeros(n, dtype=f32, device=dev)
+        self._logits = torch.zeros((n, A), dtype=f32, device=dev)
+        self._scratch_actions = torch.zeros(n, dtype=i32, device=dev)
+        self._no_mask = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.ep_count = torch.zeros(n, dtype=i32, device=dev)
+        self.ep_return_sum = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.ep_length_sum = torch.zeros(n, dtype=i32, device=dev)
+        self._primed = False
+        self._rollout = Rollout(
+            self, obs=self._obs, actions=self.actions, rewards=self._rewards, episode_starts=self._starts_all[:T],
+            values=self.values, log_probs=self.log_probs, advantages=self.advantages, returns=self.returns,
+            last_values=self.last_values, last_dones=self._starts_all[T], ep_count=self.ep_count,
+            ep_return_sum=self.ep_return_sum, ep_length_sum=self.ep_length_sum)
+
+    # ----------------------------------------------------------------- row 0
+    def _prime(self):
+        """Row 0 of the first collect: the batch's current obs (pe_reset with an empty mask
+        writes every env's current obs and resets none), as codes on an ``obs_codes`` batch;
+        every env starts an episode."""
+        torch, b = self._torch, self.batch
+        if not b.obs_codes:
+            b.reset(mask=self._no_mask, obs=self._row_views[0][0])
+        else:
+            x = b.reset(mask=self._no_mask).to(torch.float64)
+            Cn, R, G = int(b.cfg.lidar_channels), int(b.cfg.lidar_range), int(b.cfg.grid_size)
+            codes = self._row_views[0][0]
+            lid = x[:, :5 * Cn].view(-1, Cn, 5)
+            out = torch.where(lid != 0, R + 1, 0)
+            out[..., 0] = torch.round(lid[..., 0] * R).to(out.dtype)
+            codes[:, :5 * Cn] = out.view(-1, 5 * Cn).to(torch.uint8)
+            codes[:, 5 * Cn:5 * Cn + 2] = (torch.round(x[:, 5 * Cn:5 * Cn + 2] * G) + 96).to(torch.uint8)
+            codes[:, 5 * Cn + 2:] = (torch.round(x[:, 5 * Cn + 2:] * 10) + 80).to(torch.uint8)
+        self._start[0].fill_(1)
+        self._primed = True
+
+    # ----------------------------------------------------------------- hot path
+    def collect(self):
+        """Run n_steps steps and return the Rollout.  The first call starts from the batch's
+        current obs with every env flagged as an episode start; later calls continue from the
+        previous call's last row (one device copy of a row).  Everything is launched on
+        torch's current stream: no sync, and after the first call no allocation, so one
+        collect() can be captured with torch.cuda.graph and replayed (a replay repeats the
+        sampler steps of the capture)."""
+        b, pol, T = self.batch, self.policy, self.n_steps
+        if not self._primed:
+            self._prime()
+        else:
+            s = self._stride
+            self._buf[:s].copy_(self._buf[T * s:(T + 1) * s])
+        rows, views, det = self._rows, self._row_views, self.deterministic
+        boot = self.bootstrap_timeouts
+        for t in range(T):
+            a_t = self.actions[t]
+            pol.act(obs=views[t][0], deterministic=det, out=(a_t, self._logits, self.values[t]))
+            b.step(a_t, io=rows[t + 1])
+            _, rew, te, tr = views[t + 1]
+            if boot:
+                pol.act(obs=b.terminal_obs, deterministic=True,
+                        out=(self._scratch_actions, None, self.terminal_values))
+            record_device(self._logits, a_t, rew, te, tr, self.gamma, self.log_probs[t], rew, self._start[t + 1],
+                          terminal_value=self.terminal_values if boot else None, episode_return=b.episode_return,
+                          episode_length=b.episode_length, ep_count=self.ep_count, ep_return_sum=self.ep_return_sum,
+                          ep_length_sum=self.ep_length_sum)
+        pol.act(obs=views[T][0], deterministic=True, out=(self._scratch_actions, None, self.last_values))
+        gae_device(self._rewards, self.values, self._starts_all, self.last_values, self.gamma, self.gae_lambda,
+                   self.advantages, self.returns)
+        return self._rollout
+
+    def _obs_f32(self, out=None):
+        torch, b = self._torch, self.batch
+        T, n, D = self.n_steps, b.num_envs, b.obs_dim
+        if out is not None and not (type(out) is torch.Tensor and out.dtype is torch.float32 and out.is_cuda
+                                    and out.get_device() == b._dev_index and out.is_contiguous()
+                                    and tuple(out.shape) == (T * n, D)):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {(T * n, D)} on {b.device}")
+        if not b.obs_codes:
+            if out is None:
+                return self._obs.reshape(T * n, D)
+            out.view(T, n, D).copy_(self._obs)
+            return out
+        if out is None:
+            out = torch.empty((T * n, D), dtype=torch.float32, device=b.device)
+        with torch.cuda.device(b.device):
+            C.check(C.lib().pe_expand_obs_codes(b.handle, T, n, _p(self._buf), self._stride, _p(out), None, None, None,
+                                                b._stream()), "pe_expand_obs_codes")
+        return out
+
+    # ----------------------------------------------------------------- host twin
+    @staticmethod
+    def host_rollout(logits, actions, rewards, terminated, truncated, values, last_values, start0, gamma=0.99,
+                     gae_lambda=0.95, terminal_values=None, episode_return=None, episode_length=None, ep_count=None,
+                     ep_return_sum=None, ep_length_sum=None):
+        """The record and GAE host twins over T recorded steps (numpy): logits [T, n, A],
+        actions / rewards / terminated / truncated / values [T, n] (rewards as the step gave
+        them), last_values [n], start0 [n] (episode starts of step 0); terminal_values [T, n]
+        or None (no bootstrap); episode_return / episode_length [T, n] as the step left them,
+        or None.  The accumulators given (contiguous numpy i32 / f64 / i32 [n]) are updated
+        in place.  Returns a dict: log_probs, rewards, episode_starts, last_dones, advantages,
+        returns."""
+        logits = np.asarray(logits, np.float32)
+        T, n = logits.shape[:2]
+        lp = np.zeros((T, n), np.float32)
+        rw = np.zeros((T, n), np.float32)
+        st = np.zeros((T + 1, n), np.uint8)
+        st[0] = np.asarray(start0) != 0
+        for t in range(T):
+            lp[t], rw[t], st[t + 1] = host_record(
+                logits[t], actions[t], rewards[t], terminated[t], truncated[t], gamma,
+                terminal_value=None if terminal_values is None else terminal_values[t],
+                episode_return=None if episode_return is None else episode_return[t],
+                episode_length=None if episode_length is None else episode_length[t],
+                ep_count=ep_count, ep_return_sum=ep_return_sum, ep_length_sum=ep_length_sum)
+        adv, ret = host_gae(rw, values, st, last_values, gamma, gae_lambda)
+        return dict(log_probs=lp, rewards=rw, episode_starts=st[:T], last_dones=st[T], advantages=adv, returns=ret)
