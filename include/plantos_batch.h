@@ -456,6 +456,32 @@ int pe_policy_lstm_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe
                                 uint64_t seed, uint32_t env_id_offset, uint32_t t, int32_t* actions,
                                 float* head0_or_null, float* head1_or_null);
 
+/* Value-only forward: the critic tower alone, for the callers that need values and nothing
+ * else (the time-limit bootstrap and last_values of a rollout; sb3_contrib's
+ * predict_values(obs, lstm_states, episode_starts), which leaves the caller's state alone).
+ *
+ * Definition:
+ *  - Env e is selected iff (want == NULL || want[e] != 0) && !(unless != NULL && unless[e] != 0);
+ *    want / unless are device u8[n] (a step's truncated and terminated buffers fit as they are:
+ *    the envs cut by the time limit only).
+ *  - For a selected env, values[e] has exactly the bits pe_policy_forward / pe_policy_forward_lstm
+ *    would write to head1[e] for the same obs -- in the recurrent case the same obs, start flags
+ *    and current state.  The host twins' head1 is therefore the definition here too; there is no
+ *    twin of its own.
+ *  - For an env that is not selected, values[e] is not written.
+ *  - Nothing else is written: the LSTM state of no env and no tower changes, tower 0 is not
+ *    evaluated, no action is computed, the sampler is not touched.
+ * One kernel, no host sync, no allocation: graph-capturable.  A workgroup none of whose envs is
+ * selected returns at once, so a sparse selection costs about one empty launch.  PE_ERR_ARG for
+ * a one-tower policy, a NULL obs or values, and the wrong kind of policy (pe_policy_value on a
+ * recurrent policy, pe_policy_value_lstm on a feed-forward one); obs / obs_is_codes as
+ * pe_policy_forward, start_a / start_b as pe_policy_forward_lstm. */
+int pe_policy_value(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* want_or_null,
+                    const uint8_t* unless_or_null, float* values, void* stream);
+int pe_policy_value_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* start_a_or_null,
+                         const uint8_t* start_b_or_null, const uint8_t* want_or_null, const uint8_t* unless_or_null,
+                         float* values, void* stream);
+
 /* Rollout collection: what SB3 2.2.1's OnPolicyAlgorithm.collect_rollouts and
  * RolloutBuffer.compute_returns_and_advantage add to the act / step loop (A2C(n_steps=5,
  * gamma=0.99, gae_lambda=1.0) A2C_training.py:229-247; the PPO family with n_steps=1024,

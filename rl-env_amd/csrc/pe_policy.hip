@@ -1,5 +1,5 @@
 // pe_policy.hip -- batched MLP policy inference from the obs of a handle's envs to their
-// next actions: pe_policy_create / _load / _forward / _destroy of include/plantos_batch.h
+// next actions: pe_policy_create / _load / _forward / _value / _destroy of include/plantos_batch.h
 // (the definition of the outputs heads that header's "Policy inference" block; the host
 // twin is pe_policy_host.cpp and shares pe_policy_math.hpp with this file; the pieces the
 // recurrent policy of pe_policy_lstm.hip uses too are in pe_policy_impl.hpp).
@@ -81,8 +81,61 @@ __global__ __launch_bounds__(kThreads) void pe_policy_forward_kernel(FwdArgs a) 
   act_and_store<E>(hd, a.tw[0].n_out, rows, e0, a.mode, a.seed, a.env_off, a.t, a.actions, a.head0, a.head1);
 }
 
+// pe_policy_value: the forward kernel cut down to tower 1 and values[e] of the selected envs.
+// A workgroup none of whose envs is selected returns before it reads obs.  A kernel of its
+// own, so that the forward kernel's code stays as it was; the stages are the same calls.
+template <int ET>
+__global__ __launch_bounds__(kThreads) void pe_policy_value_kernel(FwdArgs a, ValueSel s) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int E = 32 * ET;
+  float* tab = lds;                    // the forward kernel's images
+  float* hd = tab + 256;
+  float* xT = hd + kHeadRows * E;
+  float* h0 = xT + a.Kp0 * E;
+  float* h1 = h0 + a.HB * E;
+  const int64_t e0 = (int64_t)blockIdx.x * E;
+  const int rows = (int)min((int64_t)E, (int64_t)a.n - e0);
+
+  const bool sel = selected(s, e0, rows);
+  if (!block_any(sel, hd)) return;  // uniform: every thread of the workgroup leaves, before any other barrier
+
+  stage_obs<E>(a.obs, a.obs_is_codes, a.tab, tab, h0, xT, e0, rows, a.D, a.SD, a.Kp0);
+  const Tower& tw = a.tw[1];
+  const float* in = xT;
+  for (int l = 0; l < tw.n_hidden; ++l) {
+    const Layer& L = tw.l[l];
+    float* out = (l & 1) ? h1 : h0;
+    hidden_layer<ET, float>(a.packed + L.off_w, a.packed + L.off_b, in, out, L.Kp >> 3, L.N >> 5, a.act);
+    __syncthreads();
+    in = out;
+  }
+  head_layer<E>(a.packed, tw.l[tw.n_hidden], tw.n_out, 1, in, hd);
+  __syncthreads();
+  store_values<E>(hd, sel, e0, s.values);
+}
+
 // ---------------------------------------------------------------- host side
 size_t lds_bytes(int E, int Kp0, int HB) { return sizeof(float) * ((size_t)256 + (size_t)E * (kHeadRows + Kp0 + 2 * HB)); }
+
+// What every launch of p reads; the sampler and output fields are left zero.
+FwdArgs fwd_args(const pe_policy* p, const void* obs, int32_t obs_is_codes) {
+  FwdArgs a{};
+  a.packed = p->mem;
+  a.tab = p->mem + p->n_packed;
+  a.obs = obs;
+  a.obs_is_codes = obs_is_codes;
+  a.n = p->h->n;
+  a.D = p->D;
+  a.SD = p->SD;
+  a.Kp0 = p->Kp0;
+  a.HB = p->HB;
+  a.n_towers = p->n_towers;
+  a.act = p->act;
+  a.env_off = p->h->cfg.env_id_offset;
+  a.tw[0] = p->tw[0];
+  a.tw[1] = p->tw[p->n_towers - 1];
+  return a;
+}
 
 }  // namespace
 
@@ -136,6 +189,11 @@ int pe_policy_create(pe_handle* h, int32_t n_towers, const pe_policy_tower* shap
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
                        : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_forward_kernel<1>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
+  if (e == hipSuccess && n_towers == 2)
+    e = env_tile == 64 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_value_kernel<2>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
+                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_value_kernel<1>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
   if (e != hipSuccess) {
     (void)hipFree(p->mem);
     delete p;
@@ -178,32 +236,17 @@ int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32
                       uint32_t t, int32_t* actions, float* head0, float* head1, void* stream) {
   if (!p || !obs || !actions) return fail(PE_ERR_ARG, "null argument");
   if (p->H) return fail(PE_ERR_ARG, "a recurrent policy runs with pe_policy_forward_lstm");
-  if (obs_is_codes != 0 && obs_is_codes != 1) return fail(PE_ERR_ARG, "obs_is_codes must be 0 or 1");
-  if (obs_is_codes && !p->h->obs_codes) return fail(PE_ERR_ARG, "obs_is_codes = 1 needs a handle created with obs_codes");
+  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
   if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
     return fail(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
   if (head1 && p->n_towers < 2) return fail(PE_ERR_ARG, "head1 needs a second tower");
-  FwdArgs a;
-  a.packed = p->mem;
-  a.tab = p->mem + p->n_packed;
-  a.obs = obs;
-  a.obs_is_codes = obs_is_codes;
-  a.n = p->h->n;
-  a.D = p->D;
-  a.SD = p->SD;
-  a.Kp0 = p->Kp0;
-  a.HB = p->HB;
-  a.n_towers = p->n_towers;
-  a.act = p->act;
+  FwdArgs a = fwd_args(p, obs, obs_is_codes);
   a.mode = mode;
   a.seed = seed;
-  a.env_off = p->h->cfg.env_id_offset;
   a.t = t;
   a.actions = actions;
   a.head0 = head0;
   a.head1 = head1;
-  a.tw[0] = p->tw[0];
-  a.tw[1] = p->tw[p->n_towers - 1];
   DevBind db(p->h->device);
   if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
   const int E = p->env_tile;
@@ -214,6 +257,26 @@ int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32
     hipLaunchKernelGGL(pe_policy_forward_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
   const hipError_t le = hipGetLastError();
   return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_forward");
+}
+
+int pe_policy_value(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* want, const uint8_t* unless,
+                    float* values, void* stream) {
+  if (!p || !obs || !values) return fail(PE_ERR_ARG, "null argument");
+  if (p->H) return fail(PE_ERR_ARG, "a recurrent policy runs with pe_policy_value_lstm");
+  if (p->n_towers < 2) return fail(PE_ERR_ARG, "values need a second tower");
+  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
+  const FwdArgs a = fwd_args(p, obs, obs_is_codes);
+  const ValueSel s{want, unless, values};
+  DevBind db(p->h->device);
+  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  const int E = p->env_tile;
+  const dim3 grid((unsigned)((a.n + E - 1) / E)), block(kThreads);
+  if (E == 64)
+    hipLaunchKernelGGL(pe_policy_value_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
+  else
+    hipLaunchKernelGGL(pe_policy_value_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
+  const hipError_t le = hipGetLastError();
+  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_value");
 }
 
 }  // extern "C"

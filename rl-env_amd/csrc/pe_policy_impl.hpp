@@ -196,11 +196,51 @@ __device__ __forceinline__ void act_and_store(const float* hd, int A, int rows, 
   }
 }
 
+// ---------------------------------------------------------------- value-only forwards
+// What pe_policy_value / pe_policy_value_lstm add to a forward's arguments.
+struct ValueSel {
+  const uint8_t* want;    // u8[n] or null: null selects every env
+  const uint8_t* unless;  // u8[n] or null: a non-zero flag deselects the env
+  float* values;          // f32[n]: written for selected envs only
+};
+
+// Whether this thread's env of the tile (e0 + threadIdx.x, for the first `rows` threads) is selected.
+__device__ __forceinline__ bool selected(const ValueSel& s, int64_t e0, int rows) {
+  const int tid = threadIdx.x;
+  if (tid >= rows) return false;
+  const int64_t e = e0 + tid;
+  return (!s.want || s.want[e] != 0) && !(s.unless && s.unless[e] != 0);
+}
+
+// Whether `mine` holds for any thread of the workgroup: the same answer in every thread.  Every
+// thread of the workgroup must call it (two barriers); `word` is an LDS word that nobody writes
+// before the workgroup's next barrier after the call.
+__device__ __forceinline__ bool block_any(bool mine, float* word) {
+  int* w = reinterpret_cast<int*>(word);
+  if (threadIdx.x == 0) *w = 0;
+  __syncthreads();
+  if (mine) *w = 1;
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane(*w) != 0;
+}
+
+// values[e] of the tile's selected envs from tower 1's head row in hd.
+template <int E>
+__device__ __forceinline__ void store_values(const float* hd, bool sel, int64_t e0, float* values) {
+  if (sel) values[e0 + threadIdx.x] = hd[(kHeadRows - 1) * E + threadIdx.x];
+}
+
 // ---------------------------------------------------------------- host side
 inline int fail(int code, const std::string& msg) { return pe_internal_set_error(code, msg.c_str()); }
 
 inline int hip_fail(hipError_t e, const char* what) {
   return fail(PE_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+inline int check_obs_kind(const pe_policy* p, int32_t obs_is_codes) {
+  if (obs_is_codes != 0 && obs_is_codes != 1) return fail(PE_ERR_ARG, "obs_is_codes must be 0 or 1");
+  if (obs_is_codes && !p->h->obs_codes) return fail(PE_ERR_ARG, "obs_is_codes = 1 needs a handle created with obs_codes");
+  return PE_OK;
 }
 
 struct DevBind {

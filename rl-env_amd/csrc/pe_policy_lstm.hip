@@ -1,6 +1,6 @@
 // pe_policy_lstm.hip -- batched recurrent policy inference (sb3_contrib's MlpLstmPolicy with
-// one LSTM layer per tower): pe_policy_create_lstm / _load_lstm / _forward_lstm and the state
-// calls of include/plantos_batch.h ("Recurrent policy inference" there is the definition;
+// one LSTM layer per tower): pe_policy_create_lstm / _load_lstm / _forward_lstm / _value_lstm and the
+// state calls of include/plantos_batch.h ("Recurrent policy inference" there is the definition;
 // the host twin is pe_policy_host.cpp).
 //
 // One fused kernel per forward, one workgroup of 8 waves per tile of E = 32 or 64 envs, as
@@ -85,7 +85,8 @@ __global__ __launch_bounds__(256) void pe_policy_lstm_pack_kernel(LstmPackArgs a
 
 // The LSTM of one tower for the tile: gates over the LDS image xh [Kp0 + H][E], cell in
 // registers, h' to hN [H][E] and, with c', to the tile's state images hs / cs [H][E] in HBM.
-template <int ET>
+// STORE = false (the value-only forward) reads the state and leaves it as it is.
+template <int ET, bool STORE>
 __device__ __forceinline__ void lstm_layer(const float* __restrict__ wp, const float* __restrict__ bias,
                                            const float* xh, float* hN, float* hs, float* cs, int KG, int H,
                                            const bool (&started)[ET], const bool (&live)[ET]) {
@@ -140,9 +141,11 @@ __device__ __forceinline__ void lstm_layer(const float* __restrict__ wp, const f
         float hn, cn;
         pe_lstm_cell(acc[0][et][r], acc[1][et][r], acc[2][et][r], acc[3][et][r], c_old, &hn, &cn);
         hN[idx] = hn;
-        if (live[et]) {
-          cs[idx] = cn;
-          hs[idx] = hn;
+        if constexpr (STORE) {
+          if (live[et]) {
+            cs[idx] = cn;
+            hs[idx] = hn;
+          }
         }
       }
     }
@@ -186,7 +189,8 @@ __global__ __launch_bounds__(kThreads) void pe_policy_lstm_forward_kernel(LstmAr
     // L: old h -> hT (zero where the env starts or lies past n), gates, cell
     for (int idx = tid; idx < H * E; idx += kThreads) hT[idx] = (l_start || le >= rows) ? 0.0f : hs[idx];
     __syncthreads();
-    lstm_layer<ET>(a.packed + a.off_lw[ti], a.packed + a.off_lb[ti], xT, hN, hs, cs, (a.Kp0 + H) >> 3, H, started, live);
+    lstm_layer<ET, true>(a.packed + a.off_lw[ti], a.packed + a.off_lb[ti], xT, hN, hs, cs, (a.Kp0 + H) >> 3, H, started,
+                         live);
     __syncthreads();
     // 1 + 2: the tower's MLP and head
     const float* in = hN;
@@ -205,6 +209,61 @@ __global__ __launch_bounds__(kThreads) void pe_policy_lstm_forward_kernel(LstmAr
   act_and_store<E>(hd, a.tw[0].n_out, rows, e0, a.mode, a.seed, a.env_off, a.t, a.actions, a.head0, a.head1);
 }
 
+// pe_policy_value_lstm: the forward kernel cut down to tower 1, from the state as it is --
+// read, never written -- and values[e] of the selected envs.  A workgroup none of whose envs
+// is selected returns before it reads obs.  A kernel of its own, so that the forward kernel's
+// code stays as it was; the stages are the same calls.
+template <int ET>
+__global__ __launch_bounds__(kThreads) void pe_policy_lstm_value_kernel(LstmArgs a, ValueSel s) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int E = 32 * ET;
+  float* tab = lds;                    // the forward kernel's images
+  float* hd = tab + 256;
+  float* xT = hd + kHeadRows * E;
+  float* hT = xT + a.Kp0 * E;
+  float* hN = hT + a.HB * E;
+  const int tid = threadIdx.x;
+  const int64_t e0 = (int64_t)blockIdx.x * E;
+  const int rows = (int)min((int64_t)E, (int64_t)a.n - e0);
+  const int H = a.H;
+
+  const bool sel = selected(s, e0, rows);
+  if (!block_any(sel, hd)) return;  // uniform: every thread of the workgroup leaves, before any other barrier
+
+  const int le = tid & (E - 1);
+  bool l_start = false;
+  if (le < rows) l_start = (a.start_a && a.start_a[e0 + le]) | (a.start_b && a.start_b[e0 + le]);
+  bool started[ET], live[ET];
+#pragma unroll
+  for (int et = 0; et < ET; ++et) {
+    const int e = et * 32 + (tid & 31);
+    live[et] = e < rows;
+    started[et] = live[et] && ((a.start_a && a.start_a[e0 + e]) | (a.start_b && a.start_b[e0 + e]));
+  }
+
+  stage_obs<E>(a.obs, a.obs_is_codes, a.tab, tab, hN, xT, e0, rows, a.D, a.SD, a.Kp0);
+
+  const Tower& tw = a.tw[1];
+  float* hs = a.state + (size_t)2 * a.n_state + (size_t)blockIdx.x * H * E;  // tower 1's h image, then its c
+  float* cs = hs + a.n_state;
+  for (int idx = tid; idx < H * E; idx += kThreads) hT[idx] = (l_start || le >= rows) ? 0.0f : hs[idx];
+  __syncthreads();
+  lstm_layer<ET, false>(a.packed + a.off_lw[1], a.packed + a.off_lb[1], xT, hN, hs, cs, (a.Kp0 + H) >> 3, H, started,
+                        live);
+  __syncthreads();
+  const float* in = hN;
+  for (int l = 0; l < tw.n_hidden; ++l) {
+    const Layer& L = tw.l[l];
+    float* out = (l & 1) ? hN : hT;
+    hidden_layer<ET, float>(a.packed + L.off_w, a.packed + L.off_b, in, out, L.Kp >> 3, L.N >> 5, a.act);
+    __syncthreads();
+    in = out;
+  }
+  head_layer<E>(a.packed, tw.l[tw.n_hidden], tw.n_out, 1, in, hd);
+  __syncthreads();
+  store_values<E>(hd, sel, e0, s.values);
+}
+
 // state image [tile][H][E] <-> the caller's [n][H]
 __global__ __launch_bounds__(256) void pe_policy_lstm_state_kernel(float* img, float* user, int n, int H, int E,
                                                                    int to_user) {
@@ -220,6 +279,36 @@ __global__ __launch_bounds__(256) void pe_policy_lstm_state_kernel(float* img, f
 
 size_t lstm_lds_bytes(int E, int Kp0, int HB) {
   return sizeof(float) * ((size_t)256 + (size_t)E * (kHeadRows + Kp0 + 2 * HB));
+}
+
+// What every launch of p reads; the sampler and output fields are left zero.
+LstmArgs lstm_args(const pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* start_a,
+                   const uint8_t* start_b) {
+  LstmArgs a{};
+  a.packed = p->mem;
+  a.tab = p->mem + p->n_packed;
+  a.obs = obs;
+  a.start_a = start_a;
+  a.start_b = start_b;
+  a.state = p->state;
+  a.n_state = p->n_state;
+  a.obs_is_codes = obs_is_codes;
+  a.n = p->h->n;
+  a.D = p->D;
+  a.SD = p->SD;
+  a.Kp0 = p->Kp0;
+  a.HB = p->HB;
+  a.H = p->H;
+  a.n_towers = p->n_towers;
+  a.act = p->act;
+  a.env_off = p->h->cfg.env_id_offset;
+  for (int i = 0; i < 2; ++i) {
+    const int s = std::min(i, p->n_towers - 1);
+    a.off_lw[i] = p->off_lw[s];
+    a.off_lb[i] = p->off_lb[s];
+    a.tw[i] = p->tw[s];
+  }
+  return a;
 }
 
 int state_copy(pe_policy* p, int tower, float* h, float* c, void* stream, int to_user, const char* what) {
@@ -306,6 +395,11 @@ int pe_policy_create_lstm(pe_handle* h, int32_t n_towers, const pe_policy_lstm* 
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
                        : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_lstm_forward_kernel<1>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
+  if (e == hipSuccess && n_towers == 2)
+    e = env_tile == 64 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_lstm_value_kernel<2>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
+                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_lstm_value_kernel<1>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
   if (e != hipSuccess) {
     (void)hipFree(p->mem);
     (void)hipFree(p->state);
@@ -355,38 +449,14 @@ int pe_policy_forward_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, 
                            float* head0, float* head1, void* stream) {
   if (!p || !obs || !actions) return fail(PE_ERR_ARG, "null argument");
   if (!p->H) return fail(PE_ERR_ARG, "a feed-forward policy runs with pe_policy_forward");
-  if (obs_is_codes != 0 && obs_is_codes != 1) return fail(PE_ERR_ARG, "obs_is_codes must be 0 or 1");
-  if (obs_is_codes && !p->h->obs_codes) return fail(PE_ERR_ARG, "obs_is_codes = 1 needs a handle created with obs_codes");
+  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
   if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
     return fail(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
   if (head1 && p->n_towers < 2) return fail(PE_ERR_ARG, "head1 needs a second tower");
-  LstmArgs a;
-  a.packed = p->mem;
-  a.tab = p->mem + p->n_packed;
-  a.obs = obs;
-  a.start_a = start_a;
-  a.start_b = start_b;
-  a.state = p->state;
-  a.n_state = p->n_state;
-  a.obs_is_codes = obs_is_codes;
-  a.n = p->h->n;
-  a.D = p->D;
-  a.SD = p->SD;
-  a.Kp0 = p->Kp0;
-  a.HB = p->HB;
-  a.H = p->H;
-  a.n_towers = p->n_towers;
-  a.act = p->act;
+  LstmArgs a = lstm_args(p, obs, obs_is_codes, start_a, start_b);
   a.mode = mode;
   a.seed = seed;
-  a.env_off = p->h->cfg.env_id_offset;
   a.t = t;
-  for (int i = 0; i < 2; ++i) {
-    const int s = std::min(i, p->n_towers - 1);
-    a.off_lw[i] = p->off_lw[s];
-    a.off_lb[i] = p->off_lb[s];
-    a.tw[i] = p->tw[s];
-  }
   a.actions = actions;
   a.head0 = head0;
   a.head1 = head1;
@@ -400,6 +470,27 @@ int pe_policy_forward_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, 
     hipLaunchKernelGGL(pe_policy_lstm_forward_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
   const hipError_t le = hipGetLastError();
   return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_forward_lstm");
+}
+
+int pe_policy_value_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* start_a,
+                         const uint8_t* start_b, const uint8_t* want, const uint8_t* unless, float* values,
+                         void* stream) {
+  if (!p || !obs || !values) return fail(PE_ERR_ARG, "null argument");
+  if (!p->H) return fail(PE_ERR_ARG, "a feed-forward policy runs with pe_policy_value");
+  if (p->n_towers < 2) return fail(PE_ERR_ARG, "values need a second tower");
+  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
+  const LstmArgs a = lstm_args(p, obs, obs_is_codes, start_a, start_b);
+  const ValueSel s{want, unless, values};
+  DevBind db(p->h->device);
+  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  const int E = p->env_tile;
+  const dim3 grid((unsigned)((a.n + E - 1) / E)), block(kThreads);
+  if (E == 64)
+    hipLaunchKernelGGL(pe_policy_lstm_value_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
+  else
+    hipLaunchKernelGGL(pe_policy_lstm_value_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
+  const hipError_t le = hipGetLastError();
+  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_value_lstm");
 }
 
 int pe_policy_lstm_reset_state(pe_policy* p, void* stream) {

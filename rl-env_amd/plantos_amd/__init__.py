@@ -8,11 +8,13 @@ Public surface:
   RecurrentPolicy   the same for LSTM policies (sb3_contrib MlpLstmPolicy), state on the device
   RolloutCollector  on-policy rollouts on the device: rollout buffer, log-probs, time-limit
                     bootstrap and GAE (SB3's collect_rollouts); returns a Rollout
+  RecurrentRolloutCollector  the same under a RecurrentPolicy (sb3_contrib's RecurrentPPO), with
+                    snapshots of the LSTM state in the Rollout
 """
 from .batch import PlantOSBatch  # noqa: F401
 from .policy import Policy, RecurrentPolicy  # noqa: F401
-from .rollout import Rollout, RolloutCollector  # noqa: F401
+from .rollout import RecurrentRolloutCollector, Rollout, RolloutCollector  # noqa: F401
 from .vec_env import PlantOSVecEnv, PlantOSVectorEnv  # noqa: F401
 
 __all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy", "Rollout",
-           "RolloutCollector"]
+           "RolloutCollector", "RecurrentRolloutCollector"]

@@ -46,6 +46,7 @@ EXPORTS = [
     "pe_policy_math_host", "pe_policy_env_tile",
     "pe_policy_create_lstm", "pe_policy_load_lstm", "pe_policy_forward_lstm", "pe_policy_lstm_reset_state",
     "pe_policy_lstm_get_state", "pe_policy_lstm_set_state", "pe_policy_lstm_forward_host",
+    "pe_policy_value", "pe_policy_value_lstm",
     "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
     "pe_logf_host",
 ]
@@ -168,6 +169,9 @@ def lib():
         L.pe_policy_lstm_get_state.argtypes = [P, I32, P, P, P]
         L.pe_policy_lstm_set_state.argtypes = [P, I32, P, P, P]
         L.pe_policy_lstm_forward_host.argtypes = [I32, I32, I32, LP, TP, I32, P, P, P, P, I32, U64, U32, U32, P, P, P]
+    if hasattr(L, "pe_policy_value"):  # (an older library loaded for a same-box A/B lacks them)
+        L.pe_policy_value.argtypes = [P, P, I32, P, P, P, P]
+        L.pe_policy_value_lstm.argtypes = [P, P, I32, P, P, P, P, P, P]
     if hasattr(L, "pe_rollout_record"):  # (an older library loaded for a same-box A/B lacks them)
         I64 = ctypes.c_int64
         rec = [I32, I32, P, P, P, P, P, P, P, P, D, P, P, P, P, P, P]
@@ -177,7 +181,7 @@ def lib():
         L.pe_rollout_gae.argtypes = gae + [P]
         L.pe_rollout_gae_host.argtypes = gae
         L.pe_logf_host.argtypes = [I32, P, P]
-    for name in ("pe_logf_host", "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
+    for name in ("pe_policy_value", "pe_policy_value_lstm", "pe_logf_host", "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
                  "pe_policy_create_lstm", "pe_policy_load_lstm", "pe_policy_forward_lstm",
                  "pe_policy_lstm_reset_state", "pe_policy_lstm_get_state", "pe_policy_lstm_set_state",
                  "pe_policy_lstm_forward_host", "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward",

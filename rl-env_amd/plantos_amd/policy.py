@@ -184,6 +184,43 @@ def _np(x):
     return x if isinstance(x, np.ndarray) else x.detach().cpu().numpy()
 
 
+def _value_args(pol, obs, select, out):
+    """The checked arguments of Policy.value / RecurrentPolicy.value: (obs, codes, want pointer,
+    unless pointer, out).  ValueError as act's."""
+    torch, b = pol._torch, pol.batch
+    n, D = b.num_envs, b.obs_dim
+    if len(pol.towers) < 2:
+        raise ValueError("a one-tower policy has no values")
+    if obs is None:
+        obs = b.obs
+    if not (type(obs) is torch.Tensor and obs.is_cuda and obs.get_device() == b._dev_index
+            and obs.is_contiguous() and tuple(obs.shape) == (n, D)
+            and (obs.dtype is torch.float32 or obs.dtype is torch.uint8)):
+        raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape {(n, D)} on {b.device}")
+    codes = obs.dtype is torch.uint8
+    if codes and not b.obs_codes:
+        raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
+    if isinstance(select, (tuple, list)):
+        if len(select) != 2:
+            raise ValueError("select must be a tensor or a pair (want, unless) of tensors")
+        want, unless = select
+    else:
+        want, unless = select, None
+    ptrs = []
+    for name, x in (("select / want", want), ("unless", unless)):
+        if x is not None and not (type(x) is torch.Tensor and x.is_cuda and x.get_device() == b._dev_index
+                                  and x.is_contiguous() and tuple(x.shape) == (n,)
+                                  and (x.dtype is torch.uint8 or x.dtype is torch.bool)):
+            raise ValueError(f"{name} must be a contiguous uint8 or bool tensor of shape {(n,)} on {b.device}")
+        ptrs.append(None if x is None else x.data_ptr())
+    if out is None:
+        out = pol.values
+    if not (type(out) is torch.Tensor and out.dtype is torch.float32 and out.is_cuda
+            and out.get_device() == b._dev_index and out.is_contiguous() and tuple(out.shape) == (n,)):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {(n,)} on {b.device}")
+    return obs, codes, ptrs[0], ptrs[1], out
+
+
 class Policy:
     """An MLP policy over the obs of a PlantOSBatch (or of a PlantOSVecEnv's batch).
 
@@ -316,6 +353,24 @@ class Policy:
         if rc:
             C.check(rc, "pe_policy_forward")
         return a, lg, v
+
+    def value(self, obs=None, select=None, out=None):
+        """The values f32 [n] alone: the value tower's head, bit for bit what `act` returns as
+        values for the same obs, without the action tower and the sampler (`t` stays).
+
+        obs: as `act`.  select: None (every env), a uint8 / bool device tensor [n] (want), or
+        a pair (want, unless): env e is evaluated iff want[e] != 0 and unless[e] == 0 -- a
+        step's (truncated, terminated) select the envs cut by the time limit only.  Entries
+        of envs not selected are left as they were, and a tile of envs none of which is
+        selected costs no work.  out: a float32 tensor [n] to write instead of the policy's
+        own values.  ValueError for a one-tower policy.  One kernel on the current stream; no
+        sync, no allocation: graph-capturable."""
+        obs, codes, want, unless, out = _value_args(self, obs, select, out)
+        rc = C.lib().pe_policy_value(self._handle(), obs.data_ptr(), int(codes), want, unless, out.data_ptr(),
+                                     self._torch.cuda.current_stream(self.batch._dev_index).cuda_stream)
+        if rc:
+            C.check(rc, "pe_policy_value")
+        return out
 
     def host_forward(self, obs_np, tensors=None, deterministic=True, t=0):
         """The host twin on f32 obs rows [n, D] (numpy) with the weights last loaded (or
@@ -591,12 +646,7 @@ class RecurrentPolicy:
         codes = obs.dtype is torch.uint8
         if codes and not b.obs_codes:
             raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
-        if isinstance(episode_start, (tuple, list)):
-            if len(episode_start) != 2:
-                raise ValueError("episode_start must be a tensor or a pair of tensors")
-            sa, sb = self._flag(episode_start[0], "episode_start[0]"), self._flag(episode_start[1], "episode_start[1]")
-        else:
-            sa, sb = self._flag(episode_start, "episode_start"), None
+        sa, sb = self._starts(episode_start)
         a, lg, v = out if out is not None else (self.actions, self.logits, self.values)
         A = self.towers[0][-1]
         for name, x, dt, shape in (("actions", a, torch.int32, (n,)), ("logits", lg, torch.float32, (n, A)),
@@ -623,22 +673,58 @@ class RecurrentPolicy:
             C.check(rc, "pe_policy_forward_lstm")
         return a, lg, v
 
+    def _starts(self, episode_start):
+        if isinstance(episode_start, (tuple, list)):
+            if len(episode_start) != 2:
+                raise ValueError("episode_start must be a tensor or a pair of tensors")
+            return self._flag(episode_start[0], "episode_start[0]"), self._flag(episode_start[1], "episode_start[1]")
+        return self._flag(episode_start, "episode_start"), None
+
+    def value(self, obs=None, episode_start=None, select=None, out=None):
+        """The values f32 [n] alone, from the LSTM state as it is: bit for bit what `act` would
+        return as values for the same obs, flags and state -- but the state of no env and no
+        tower changes, the actor tower is not evaluated and the sampler's `t` stays
+        (sb3_contrib's predict_values).
+
+        obs, episode_start: as `act`.  select, out: as Policy.value.  ValueError for an
+        actor-only policy.  One kernel on the current stream; no sync, no allocation:
+        graph-capturable."""
+        obs, codes, want, unless, out = _value_args(self, obs, select, out)
+        sa, sb = self._starts(episode_start)
+        rc = C.lib().pe_policy_value_lstm(self._handle(), obs.data_ptr(), int(codes), sa, sb, want, unless,
+                                          out.data_ptr(), self._stream())
+        if rc:
+            C.check(rc, "pe_policy_value_lstm")
+        return out
+
     def reset_states(self):
         """Zero the state of every env and tower (ordered on the current stream)."""
         C.check(C.lib().pe_policy_lstm_reset_state(self._handle(), self._stream()), "pe_policy_lstm_reset_state")
 
-    def get_states(self):
+    def get_states(self, out=None):
         """[(h, c), ..] per tower: fresh device tensors f32 [n, H] (SB3's lstm_states, without
-        the leading layer axis)."""
+        the leading layer axis).  out: [(h, c), ..] of preallocated contiguous float32 device
+        tensors [n, H] to write instead (no allocation: graph-capturable); it is returned."""
         torch, b = self._torch, self.batch
-        out = []
+        shape = (b.num_envs, self.hidden)
+        if out is not None:
+            if len(out) != len(self.towers) or any(len(pair) != 2 for pair in out):
+                raise ValueError(f"out must be {len(self.towers)} (h, c) pairs")
+            for x in (x for pair in out for x in pair):
+                if not (type(x) is torch.Tensor and x.dtype is torch.float32 and x.is_cuda
+                        and x.get_device() == b._dev_index and x.is_contiguous() and tuple(x.shape) == shape):
+                    raise ValueError(f"out tensors must be contiguous float32 of shape {shape} on {b.device}")
+        res = []
         for i in range(len(self.towers)):
-            h = torch.empty((b.num_envs, self.hidden), dtype=torch.float32, device=b.device)
-            c = torch.empty_like(h)
+            if out is not None:
+                h, c = out[i]
+            else:
+                h = torch.empty(shape, dtype=torch.float32, device=b.device)
+                c = torch.empty_like(h)
             C.check(C.lib().pe_policy_lstm_get_state(self._handle(), i, h.data_ptr(), c.data_ptr(), self._stream()),
                     "pe_policy_lstm_get_state")
-            out.append((h, c))
-        return out
+            res.append((h, c))
+        return res
 
     def set_states(self, states):
         """Replace the state: [(h, c), ..] per tower, [n, H] each (device tensors are read in

@@ -16,15 +16,21 @@ Learners stay out of scope: the Rollout is the data they consume.
         learner.update(ro.obs_f32(), ro.actions, ro.advantages, ro.returns, ro.log_probs, ro.values)
         policy.load(learner.state_dict())
 
+RecurrentRolloutCollector is the same for a two-tower RecurrentPolicy (sb3_contrib's
+RecurrentPPO.collect_rollouts): the LSTM state advances with the steps, the bootstrap and
+last_values come from the value-only forward, which leaves it alone, and the Rollout carries
+snapshots of the state for the learner.
+
 Every output is defined bit for bit by the host twins (`host_record`, `host_gae`,
-`RolloutCollector.host_rollout`), which need no device.
+`RolloutCollector.host_rollout`, `RecurrentRolloutCollector.host_rollout`), which need no
+device.
 """
 import ctypes
 
 import numpy as np
 
 from . import _capi as C
-from .policy import Policy, RecurrentPolicy
+from .policy import Policy, RecurrentPolicy, lstm_host_forward
 
 ROW_ALIGN = 512  # bytes: every row of the buffer starts as aligned as a fresh torch allocation
 
@@ -129,7 +135,9 @@ class Rollout:
     where it applies), episode_starts u8 [T, n] (strided), values, log_probs, advantages,
     returns f32 [T, n], last_values f32 [n], last_dones u8 [n], and the per-env episode
     accumulators since the collector was made: ep_count i32 [n], ep_return_sum f64 [n],
-    ep_length_sum i32 [n]."""
+    ep_length_sum i32 [n].  lstm_states: None, or from a RecurrentRolloutCollector
+    [(h, c), ..] per tower, f32 [1, n, H] (the state before step 0) or [T, n, H] (before
+    every step), as `state_snapshots` asked."""
 
     FIELDS = ("obs", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns",
               "last_values", "last_dones", "ep_count", "ep_return_sum", "ep_length_sum")
@@ -138,6 +146,7 @@ class Rollout:
         self._c = collector
         for k in self.FIELDS:
             setattr(self, k, fields[k])
+        self.lstm_states = fields.get("lstm_states")
 
     def obs_f32(self, out=None):
         """The obs as float32 [T * n, D] (step-major).  On an ``obs_codes`` batch: one
@@ -146,27 +155,14 @@ class Rollout:
         return self._c._obs_f32(out)
 
 
-class RolloutCollector:
-    """Collects `n_steps` steps of every env of a PlantOSBatch (or a PlantOSVecEnv's batch) under
-    a two-tower Policy, entirely on the device.
+class _Collector:
+    """What the two collectors share: the argument checks after the policy's kind, the storage
+    rows, row 0 and the obs view."""
 
-    gamma / gae_lambda: the GAE parameters; bootstrap_timeouts: add gamma * V(terminal obs) to
-    the reward of an episode cut by the time limit only (SB3's TimeLimit.truncated handling);
-    deterministic: argmax actions instead of the policy's Philox sampler (whose step counter
-    advances by one per step, across collects).  Storage is allocated here, once.  ValueError
-    for a one-tower policy (no values), a RecurrentPolicy, n_steps < 1, a policy of another
-    batch, or a batch without autoreset."""
-
-    def __init__(self, batch_or_venv, policy, n_steps, gamma=0.99, gae_lambda=0.95, bootstrap_timeouts=True,
-                 deterministic=False):
+    def _setup(self, batch, policy, n_steps, gamma, gae_lambda, bootstrap_timeouts, deterministic):
         import torch
         self._torch = torch
-        b = self.batch = getattr(batch_or_venv, "batch", batch_or_venv)
-        if isinstance(policy, RecurrentPolicy):
-            raise ValueError("recurrent rollouts are not supported: the bootstrap needs a value forward that does not "
-                             "advance the LSTM state")
-        if not isinstance(policy, Policy):
-            raise ValueError("policy must be a plantos_amd.Policy")
+        b = self.batch = batch
         if len(policy.towers) != 2:
             raise ValueError("a rollout needs values: the policy must have a value tower")
         if policy.batch is not b:
@@ -207,7 +203,6 @@ class RolloutCollector:
         self.last_values = torch.zeros(n, dtype=f32, device=dev)
         self.terminal_values = torch.zeros(n, dtype=f32, device=dev)
         self._logits = torch.zeros((n, A), dtype=f32, device=dev)
-        self._scratch_actions = torch.zeros(n, dtype=i32, device=dev)
         self._no_mask = torch.zeros(n, dtype=torch.uint8, device=dev)
         self.ep_count = torch.zeros(n, dtype=i32, device=dev)
         self.ep_return_sum = torch.zeros(n, dtype=torch.float64, device=dev)
@@ -218,6 +213,15 @@ class RolloutCollector:
             values=self.values, log_probs=self.log_probs, advantages=self.advantages, returns=self.returns,
             last_values=self.last_values, last_dones=self._starts_all[T], ep_count=self.ep_count,
             ep_return_sum=self.ep_return_sum, ep_length_sum=self.ep_length_sum)
+
+    def _begin(self):
+        """Row 0 of a collect: primed from the batch the first time, else the previous collect's
+        last row (one device copy of a row)."""
+        if not self._primed:
+            self._prime()
+        else:
+            s = self._stride
+            self._buf[:s].copy_(self._buf[self.n_steps * s:(self.n_steps + 1) * s])
 
     # ----------------------------------------------------------------- row 0
     def _prime(self):
@@ -240,39 +244,6 @@ class RolloutCollector:
         self._start[0].fill_(1)
         self._primed = True
 
-    # ----------------------------------------------------------------- hot path
-    def collect(self):
-        """Run n_steps steps and return the Rollout.  The first call starts from the batch's
-        current obs with every env flagged as an episode start; later calls continue from the
-        previous call's last row (one device copy of a row).  Everything is launched on
-        torch's current stream: no sync, and after the first call no allocation, so one
-        collect() can be captured with torch.cuda.graph and replayed (a replay repeats the
-        sampler steps of the capture)."""
-        b, pol, T = self.batch, self.policy, self.n_steps
-        if not self._primed:
-            self._prime()
-        else:
-            s = self._stride
-            self._buf[:s].copy_(self._buf[T * s:(T + 1) * s])
-        rows, views, det = self._rows, self._row_views, self.deterministic
-        boot = self.bootstrap_timeouts
-        for t in range(T):
-            a_t = self.actions[t]
-            pol.act(obs=views[t][0], deterministic=det, out=(a_t, self._logits, self.values[t]))
-            b.step(a_t, io=rows[t + 1])
-            _, rew, te, tr = views[t + 1]
-            if boot:
-                pol.act(obs=b.terminal_obs, deterministic=True,
-                        out=(self._scratch_actions, None, self.terminal_values))
-            record_device(self._logits, a_t, rew, te, tr, self.gamma, self.log_probs[t], rew, self._start[t + 1],
-                          terminal_value=self.terminal_values if boot else None, episode_return=b.episode_return,
-                          episode_length=b.episode_length, ep_count=self.ep_count, ep_return_sum=self.ep_return_sum,
-                          ep_length_sum=self.ep_length_sum)
-        pol.act(obs=views[T][0], deterministic=True, out=(self._scratch_actions, None, self.last_values))
-        gae_device(self._rewards, self.values, self._starts_all, self.last_values, self.gamma, self.gae_lambda,
-                   self.advantages, self.returns)
-        return self._rollout
-
     def _obs_f32(self, out=None):
         torch, b = self._torch, self.batch
         T, n, D = self.n_steps, b.num_envs, b.obs_dim
@@ -291,6 +262,61 @@ class RolloutCollector:
             C.check(C.lib().pe_expand_obs_codes(b.handle, T, n, _p(self._buf), self._stride, _p(out), None, None, None,
                                                 b._stream()), "pe_expand_obs_codes")
         return out
+
+
+class RolloutCollector(_Collector):
+    """Collects `n_steps` steps of every env of a PlantOSBatch (or a PlantOSVecEnv's batch) under
+    a two-tower Policy, entirely on the device.
+
+    gamma / gae_lambda: the GAE parameters; bootstrap_timeouts: add gamma * V(terminal obs) to
+    the reward of an episode cut by the time limit only (SB3's TimeLimit.truncated handling);
+    deterministic: argmax actions instead of the policy's Philox sampler (whose step counter
+    advances by one per step, across collects).  Storage is allocated here, once.  ValueError
+    for a one-tower policy (no values), a RecurrentPolicy (RecurrentRolloutCollector collects
+    those), n_steps < 1, a policy of another batch, or a batch without autoreset.
+
+    The bootstrap and last_values run the value-only forward (Policy.value): the critic tower
+    alone, and for the bootstrap only the tiles that hold an env cut by the time limit only.
+    `terminal_values` therefore keeps stale entries for every other env; pe_rollout_record
+    reads it only where truncated && !terminated (record_reward, pe_rollout_math.hpp), so no
+    stale entry reaches a reward."""
+
+    def __init__(self, batch_or_venv, policy, n_steps, gamma=0.99, gae_lambda=0.95, bootstrap_timeouts=True,
+                 deterministic=False):
+        if isinstance(policy, RecurrentPolicy):
+            raise ValueError("a RecurrentPolicy's rollouts are collected by RecurrentRolloutCollector")
+        if not isinstance(policy, Policy):
+            raise ValueError("policy must be a plantos_amd.Policy")
+        self._setup(getattr(batch_or_venv, "batch", batch_or_venv), policy, n_steps, gamma, gae_lambda,
+                    bootstrap_timeouts, deterministic)
+
+    # ----------------------------------------------------------------- hot path
+    def collect(self):
+        """Run n_steps steps and return the Rollout.  The first call starts from the batch's
+        current obs with every env flagged as an episode start; later calls continue from the
+        previous call's last row (one device copy of a row).  Everything is launched on
+        torch's current stream: no sync, and after the first call no allocation, so one
+        collect() can be captured with torch.cuda.graph and replayed (a replay repeats the
+        sampler steps of the capture)."""
+        b, pol, T = self.batch, self.policy, self.n_steps
+        self._begin()
+        rows, views, det = self._rows, self._row_views, self.deterministic
+        boot = self.bootstrap_timeouts
+        for t in range(T):
+            a_t = self.actions[t]
+            pol.act(obs=views[t][0], deterministic=det, out=(a_t, self._logits, self.values[t]))
+            b.step(a_t, io=rows[t + 1])
+            _, rew, te, tr = views[t + 1]
+            if boot:
+                pol.value(obs=b.terminal_obs, select=(tr, te), out=self.terminal_values)
+            record_device(self._logits, a_t, rew, te, tr, self.gamma, self.log_probs[t], rew, self._start[t + 1],
+                          terminal_value=self.terminal_values if boot else None, episode_return=b.episode_return,
+                          episode_length=b.episode_length, ep_count=self.ep_count, ep_return_sum=self.ep_return_sum,
+                          ep_length_sum=self.ep_length_sum)
+        pol.value(obs=views[T][0], out=self.last_values)
+        gae_device(self._rewards, self.values, self._starts_all, self.last_values, self.gamma, self.gae_lambda,
+                   self.advantages, self.returns)
+        return self._rollout
 
     # ----------------------------------------------------------------- host twin
     @staticmethod
@@ -319,3 +345,132 @@ class RolloutCollector:
                 ep_count=ep_count, ep_return_sum=ep_return_sum, ep_length_sum=ep_length_sum)
         adv, ret = host_gae(rw, values, st, last_values, gamma, gae_lambda)
         return dict(log_probs=lp, rewards=rw, episode_starts=st[:T], last_dones=st[T], advantages=adv, returns=ret)
+
+
+class RecurrentRolloutCollector(_Collector):
+    """Collects `n_steps` steps of every env of a PlantOSBatch (or a PlantOSVecEnv's batch) under
+    a two-tower RecurrentPolicy, entirely on the device: sb3_contrib's
+    RecurrentPPO.collect_rollouts and compute_returns_and_advantage.
+
+    gamma / gae_lambda / bootstrap_timeouts / deterministic: as RolloutCollector's.  Per step
+    the policy's `act` reads the row's obs and its episode-start flags and advances the LSTM
+    state.  The bootstrap is the critic on the terminal obs from the state AFTER that forward,
+    with no start flag and the state not advanced (predict_values(terminal_obs,
+    terminal_lstm_state, episode_starts=[False])); last_values is the critic on the last obs
+    with the last step's done flags as start flags, the state again left alone.  Both are
+    RecurrentPolicy.value.
+
+    Row 0 of the first collect flags every env as an episode start, so the first forward reads
+    a zero state whatever the policy held; later collects continue from the previous one's
+    last row and from the policy's live state.
+
+    state_snapshots: what `Rollout.lstm_states` holds, [(h, c), ..] per tower, raw (before the
+    start flags mask it: sb3_contrib's _last_lstm_states).  "first": the state before step 0,
+    f32 [1, n, H] each.  "all": the state before every step, f32 [T, n, H] each, which is
+    16 * T * n * H bytes for the two towers (h and c, 4 bytes each), allocated here.
+
+    ValueError for a policy that is no RecurrentPolicy or has no critic tower, a
+    state_snapshots other than "first" / "all", and what RolloutCollector refuses."""
+
+    def __init__(self, batch_or_venv, policy, n_steps, gamma=0.99, gae_lambda=0.95, bootstrap_timeouts=True,
+                 deterministic=False, state_snapshots="first"):
+        if not isinstance(policy, RecurrentPolicy):
+            raise ValueError("policy must be a plantos_amd.RecurrentPolicy (RolloutCollector collects a Policy's rollouts)")
+        if state_snapshots not in ("first", "all"):
+            raise ValueError(f"state_snapshots must be 'first' or 'all', got {state_snapshots!r}")
+        self._setup(getattr(batch_or_venv, "batch", batch_or_venv), policy, n_steps, gamma, gae_lambda,
+                    bootstrap_timeouts, deterministic)
+        torch, b = self._torch, self.batch
+        self.state_snapshots = state_snapshots
+        S = self.n_steps if state_snapshots == "all" else 1
+        shape = (S, b.num_envs, policy.hidden)
+        self.lstm_states = [(torch.zeros(shape, dtype=torch.float32, device=b.device),
+                             torch.zeros(shape, dtype=torch.float32, device=b.device)) for _ in policy.towers]
+        self._snap = [[(h[t], c[t]) for h, c in self.lstm_states] for t in range(S)]
+        self._rollout.lstm_states = self.lstm_states
+
+    # ----------------------------------------------------------------- hot path
+    def collect(self):
+        """Run n_steps steps and return the Rollout: RolloutCollector.collect's contract (current
+        stream, no sync, no allocation after the first call, graph-capturable)."""
+        b, pol, T = self.batch, self.policy, self.n_steps
+        self._begin()
+        rows, views, det = self._rows, self._row_views, self.deterministic
+        boot = self.bootstrap_timeouts
+        for t in range(T):
+            if t < len(self._snap):
+                pol.get_states(out=self._snap[t])
+            a_t = self.actions[t]
+            pol.act(obs=views[t][0], episode_start=self._start[t], deterministic=det,
+                    out=(a_t, self._logits, self.values[t]))
+            b.step(a_t, io=rows[t + 1])
+            _, rew, te, tr = views[t + 1]
+            if boot:
+                pol.value(obs=b.terminal_obs, select=(tr, te), out=self.terminal_values)
+            record_device(self._logits, a_t, rew, te, tr, self.gamma, self.log_probs[t], rew, self._start[t + 1],
+                          terminal_value=self.terminal_values if boot else None, episode_return=b.episode_return,
+                          episode_length=b.episode_length, ep_count=self.ep_count, ep_return_sum=self.ep_return_sum,
+                          ep_length_sum=self.ep_length_sum)
+        pol.value(obs=views[T][0], episode_start=self._start[T], out=self.last_values)
+        gae_device(self._rewards, self.values, self._starts_all, self.last_values, self.gamma, self.gae_lambda,
+                   self.advantages, self.returns)
+        return self._rollout
+
+    # ----------------------------------------------------------------- host twin
+    @staticmethod
+    def host_rollout(hidden, towers, lstm_tensors, mlp_tensors, activation, obs, last_obs, terminal_obs, actions,
+                     rewards, terminated, truncated, start0, states0=None, gamma=0.99, gae_lambda=0.95,
+                     bootstrap_timeouts=True, state_snapshots="first", episode_return=None, episode_length=None,
+                     ep_count=None, ep_return_sum=None, ep_length_sum=None):
+        """The recurrent collect in numpy, no device: the policy's host twin (lstm_host_forward)
+        stepped over T recorded steps with the carried states, then RolloutCollector.host_rollout
+        (host_record / host_gae).
+
+        hidden / towers / lstm_tensors / mlp_tensors / activation: the weights, as
+        lstm_host_forward takes them.  obs f32 [T, n, D] (what the policy read at each step),
+        last_obs f32 [n, D] (the obs after the last step), terminal_obs f32 [T, n, D] (the
+        step's terminal obs; rows of envs not cut by the time limit are evaluated too and
+        read by nothing), actions i32 [T, n] (the actions taken: the twin does not sample),
+        rewards / terminated / truncated [T, n] as the step gave them, start0 [n] (episode
+        starts of step 0), states0 [(h, c), ..] per tower f32 [n, H] (None: zeros), the rest
+        as RolloutCollector.host_rollout.  The terminal values and last_values are computed on
+        COPIES of the carried states: only the per-step forward advances them.
+
+        Returns RolloutCollector.host_rollout's dict plus values [T, n], terminal_values [T, n]
+        (None without the bootstrap), last_values [n], lstm_states (the snapshots,
+        [(h, c), ..] of [1, n, H] or [T, n, H]) and final_states [(h, c), ..]."""
+        if state_snapshots not in ("first", "all"):
+            raise ValueError(f"state_snapshots must be 'first' or 'all', got {state_snapshots!r}")
+        obs = np.asarray(obs, np.float32)
+        T, n = obs.shape[:2]
+        nt = len(towers)
+        fwd = lambda x, st, start: lstm_host_forward(hidden, towers, lstm_tensors, mlp_tensors, activation, x,  # noqa: E731
+                                                     states=st, episode_start=start)
+        copy = lambda st: [(h.copy(), c.copy()) for h, c in st]  # noqa: E731
+        if states0 is None:
+            states = [(np.zeros((n, hidden), np.float32), np.zeros((n, hidden), np.float32)) for _ in range(nt)]
+        else:
+            states = [(np.array(h, np.float32), np.array(c, np.float32)) for h, c in states0]
+        st = np.zeros((T + 1, n), np.uint8)
+        st[0] = np.asarray(start0) != 0
+        st[1:] = (np.asarray(terminated) != 0) | (np.asarray(truncated) != 0)
+        A = towers[0][-1]
+        logits = np.zeros((T, n, A), np.float32)
+        values = np.zeros((T, n), np.float32)
+        tv = np.zeros((T, n), np.float32) if bootstrap_timeouts else None
+        snaps = []
+        for t in range(T):
+            if t == 0 or state_snapshots == "all":
+                snaps.append(copy(states))
+            (_, logits[t], values[t]), states = fwd(obs[t], states, st[t])
+            if bootstrap_timeouts:
+                tv[t] = fwd(terminal_obs[t], copy(states), None)[0][2]
+        last_values = fwd(last_obs, copy(states), st[T])[0][2]
+        out = RolloutCollector.host_rollout(
+            logits, actions, rewards, terminated, truncated, values, last_values, start0, gamma, gae_lambda,
+            terminal_values=tv, episode_return=episode_return, episode_length=episode_length, ep_count=ep_count,
+            ep_return_sum=ep_return_sum, ep_length_sum=ep_length_sum)
+        out.update(values=values, terminal_values=tv, last_values=last_values, final_states=states,
+                   lstm_states=[(np.stack([s[i][0] for s in snaps]), np.stack([s[i][1] for s in snaps]))
+                                for i in range(nt)])
+        return out
