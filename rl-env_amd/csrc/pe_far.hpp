@@ -31,18 +31,13 @@
 // byte tile (~34 KB at 64x64 / 64 rays), so the 1024 workgroups of a 65536-env batch
 // are resident at once (4 per CU); the cost that remains is the grid rows
 // (~2 KB per env-step with the 2R pad) and the obs stream.
-// (a fragment of plantos_batch.hip's anonymous namespace, like pe_pipe.hpp)
+// (a fragment of plantos_batch.hip's anonymous namespace)
 #pragma once
 
 constexpr int kFarWaves = 4;
-#ifndef PE_FAR_INFO_REG
-#define PE_FAR_INFO_REG 0  // the terminal-info rows register-staged by the info wave (round 6 A/B: slower)
-#endif
-#ifndef PE_FAR_ROW_BATCH
-#define PE_FAR_ROW_BATCH 33  // one batch: the compiler's schedule (9: 55.1 us, 12: 54.3, 17: 54.6, 33: 53.7 at
-                             // 64x64/C64/R32, same box, profiles/r5f/, r5h/)
-#endif
-constexpr int kFarRowBatch = PE_FAR_ROW_BATCH;  // quadrant rows per load batch
+// quadrant rows per load batch.  33, one batch: the compiler's schedule (9: 55.1 us, 12: 54.3, 17: 54.6,
+// 33: 53.7 at 64x64/C64/R32, same box, profiles/r5f/, r5h/)
+constexpr int kFarRowBatch = 33;
 constexpr int kFarRow32 = 2 * kCoopWPR;  // u32 words per padded grid row: the kernel takes G + 2R in (96, 128]
 
 template <int C, int R>
@@ -109,16 +104,10 @@ __host__ __device__ constexpr int far_stage_units(int G, int WPR, int C) {
   return pf_stage_units(G, WPR, ((5 * C + 27) + 15) & ~15, false);
 }
 __host__ __device__ constexpr int far_stage_off(int G, int WPR, int C, int R) { return far_ctab_off(G, WPR, C, R) + 256; }
-// (round 6) after the record: the env's current grid rows for its terminal info, register-
-// staged by the info wave in round 2 (pe_step_far info_reg), then one unit of the done env's
-// post-step scalars and one of its wfix, parked by the commit wave for the info wave
-__host__ __device__ constexpr int far_info_park_unit(int G, int WPR, int C) {
-  return far_stage_units(G, WPR, C) + pf_grid_units(G, WPR);
-}
 __host__ __device__ constexpr int far_lds_floats(int G, int WPR, int C, int R) {
   // (whole 64-unit LDS-DMA instructions: every lane of the last one writes its unit)
   return far_stage_off(G, WPR, C, R) +
-         4 * 64 * (((PE_FAR_INFO_REG ? far_info_park_unit(G, WPR, C) + 2 : far_stage_units(G, WPR, C)) + 63) / 64);
+         4 * 64 * ((far_stage_units(G, WPR, C) + 63) / 64);
 }
 
 // Quadrant W's rays for this lane's env at the post-move position (xp, yp): first hit
@@ -322,19 +311,6 @@ __device__ __attribute__((noinline)) uint4 far_done(const void* ka, int tile_off
   return quad_done_path<kFarWaves, false, (D + 63) / 64, true, true>(ka, tile_off, C, R, lane, wv, kFarWaves - 1, e0,
                                                                      done, sp, ret, ndone, wfix, ctab, stage, stage_info);
 }
-#if PE_FAR_INFO_REG
-// (the A/B form: the info wave writes the terminal info from the rows it staged)
-template <int C, int R>
-__device__ __attribute__((noinline)) uint4 far_done_iw(const void* ka, int tile_off, int lane, int wv, int64_t e0,
-                                                       bool done, uint4 sp, double ret, int ndone, bool wfix,
-                                                       const float* ctab, const float* stage, bool stage_info,
-                                                       bool info_iw, int park_unit) {
-  constexpr int D = 5 * C + 27;
-  return quad_done_path<kFarWaves, false, (D + 63) / 64, true>(
-      ka, tile_off, C, R, lane, wv, kFarWaves - 1, e0, done, sp, ret, ndone, wfix, ctab, stage, stage_info, -1,
-      nullptr, nullptr, -1, false, info_iw, stage ? stage + 4 * park_unit : nullptr);
-}
-#endif
 
 template <int C, int R>
 __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
@@ -354,7 +330,7 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
   const int64_t e = e0 + lane;
   const bool live = e < a.n;
   if (a.stagger) {  // de-phase the resident workgroups of a CU (speed only), as pe_step_quad
-    const int qg = (int)(blockIdx.x * PE_STAGGER_GROUPS / gridDim.x);
+    const int qg = (int)(blockIdx.x * kStaggerGroups / gridDim.x);
     for (int i = 0; i < qg * a.stagger; ++i) __builtin_amdgcn_s_sleep(8);
   }
   // ---- round 1 (every wave; unconditional loads at an index clamped into the batch)
@@ -399,25 +375,14 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
   const bool stage_ok = a.pf.scal && quad_coop(a, 1) && e0 + LS <= a.n;  // full block: every lane live
   constexpr bool stage_info = false;  // (see far_stage_units)
   int npred = 0;
-  // (round 6) the predicted env's current grid rows for its terminal info, register-staged
-  // by the info wave (two 16-B units per lane, written to LDS before the march): the info
-  // wave then writes the terminal info beside the commit wave's reset, instead of the commit
-  // wave loading the rows after the done barrier (a round trip on the one-done block's path)
-  const int ng_s = pf_grid_units(g.G, g.WPR);
-  // (measured slower here: 64x64/C64/R32 desync 60.0 -> 61.0 us, sync 52.8 -> 53.2, profiles/r6e/ --
-  // the kernel is at its register cap; A/B: -DPE_FAR_INFO_REG=1)
-  const bool info_reg = PE_FAR_INFO_REG && stage_ok && !st.cur && a.tinfo != nullptr && ng_s <= 128;
-  uint4 iq0 = make_uint4(0u, 0u, 0u, 0u), iq1 = iq0;
+  // (the env's current grid rows register-staged by the info wave, as the byte-coded pe_step_quad's,
+  // measured slower here: 64x64/C64/R32 desync 60.0 -> 61.0 us, sync 52.8 -> 53.2, profiles/r6e/ --
+  // the kernel is at its register cap)
   if (stage_ok) {
     const uint64_t pm = __ballot(s.step + 1 >= a.rl.max_steps);
     npred = __popcll(pm);
     if (wv == CW && npred == 1)
       pf_stage_issue(a.pf, st, g, e0 + (__ffsll((unsigned long long)pm) - 1), stage, lane, stage_info);
-    if (info_reg && wv == kQuadInfoWave && npred == 1) {
-      const uint4* src = reinterpret_cast<const uint4*>(st.grid + (e0 + (__ffsll((unsigned long long)pm) - 1)) * g.gstride);
-      iq0 = src[lane < ng_s ? lane : ng_s - 1];
-      iq1 = src[lane + 64 < ng_s ? lane + 64 : ng_s - 1];
-    }
   }
   const int vw0 = (4 * m.ybv) >> 5, vo = (4 * m.ybv) & 31;
   uint32_t cv[2][3][2];  // [slice row t][candidate k][word]
@@ -458,11 +423,6 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
   // one).  (The candidate slice rows and the rays' rows may see the new bytes: the slice
   // centre is rebuilt from nib, the watered cell's fix is idempotent.)
   asm volatile("s_barrier" ::"v"(vt), "v"(gt), "v"(gc) : "memory");
-  if (info_reg && wv == kQuadInfoWave && npred == 1) {  // (into LDS before the march: no registers across it)
-    uint4* d = reinterpret_cast<uint4*>(stage) + far_stage_units(g.G, g.WPR, C);
-    if (lane < ng_s) d[lane] = iq0;
-    if (lane + 64 < ng_s) d[lane + 64] = iq1;
-  }
   uint8_t* row = rows + lane * D;
   bool done = false, wfix = false;
   uint32_t* park = reinterpret_cast<uint32_t*>(smem + far_park_off(g.G, g.WPR, C, R));
@@ -502,9 +462,6 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
       }
     }
     // ---- round 3 + the rays of this wave's quadrant
-#if defined(PE_FAR_PROBE) && PE_FAR_PROBE == 1  // timing probe (wrong obs): no rays
-    if (false)
-#endif
     switch (wv) {
       case 0: far_sector<C, R, 0>(gb32, g.G, xp, yp, watered, row); break;
       case 1: far_sector<C, R, 1>(gb32, g.G, xp, yp, watered, row); break;
@@ -513,18 +470,9 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
     }
   }
   // ---- DummyVecEnv auto-reset (rare): the commit wave's done mask in dist[70..71]
-  const int park_unit = far_info_park_unit(g.G, g.WPR, C);
   if (wv == CW) {
     const uint64_t dm = __ballot(done);
     if (lane == 0) reinterpret_cast<uint64_t*>(smem)[35] = dm;
-    if (info_reg && npred == 1 && __popcll(dm) == 1 && done) {  // the one done env's scalars for the info wave
-      float* pk = stage + 4 * park_unit;  // (from the commit wave's park words: no registers across the march)
-      pk[0] = __int_as_float((int)park[lane]);
-      pk[1] = __int_as_float((int)park[64 + lane]);
-      pk[2] = __int_as_float((int)park[128 + lane]);
-      pk[3] = __int_as_float((int)park[192 + lane]);
-      pk[4] = __int_as_float((int)wfix);
-    }
   }
   // the block barrier without a memory fence (see pe_step_quad)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -542,18 +490,10 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
       rv = __hiloint2double((int)park[320 + lane], (int)park[256 + lane]);
     }
     const bool staged = stage_ok && npred == 1 && ndone == 1;  // then the done env is the predicted one
-#if PE_FAR_INFO_REG
-    sp = far_done_iw<C, R>(kernargs(), tile_off, lane, wv, e0, done, sp, rv, ndone, wfix, ctab, staged ? stage : nullptr,
-                           staged && stage_info, staged && info_reg, park_unit);
-#else
     sp = far_done<C, R>(kernargs(), tile_off, lane, wv, e0, done, sp, rv, ndone, wfix, ctab, staged ? stage : nullptr,
                         staged && stage_info);
-#endif
   }
   if (wv == CW) __builtin_amdgcn_s_waitcnt(0x0F70);  // tracked vmcnt(0): no wait inside the store loop
-#if defined(PE_FAR_PROBE) && PE_FAR_PROBE == 2  // timing probe (no obs): no tile store
-  if (false)
-#endif
   if (a.obs_codes)
     store_tile_bytes(rows, a.obs_codes + e0 * D, (int)valid, D, (int)threadIdx.x, (int)blockDim.x);
   else

@@ -926,7 +926,6 @@ constexpr size_t kMctsLdsMax = 64 * 1024;  // >= 2 workgroups per CU
 
 struct pe_mcts {
   pe_handle* h;
-  int force_global;  // PE_MCTS_GLOBAL=1 (PE_DEBUG_KNOBS builds): the global-memory sim cells even when LDS fits
   int n_sims, max_depth;
   double c;
   void* mem;
@@ -976,10 +975,6 @@ int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t 
   m->csg = reinterpret_cast<uint32_t*>(q + al(n * ggp) + al(n * GG * 4));
   m->ggp = (int)ggp;
   m->h = h;
-  m->force_global = 0;
-#ifdef PE_DEBUG_KNOBS  // A/B builds only (tools/ab_build.sh): the product library reads no environment variable
-  m->force_global = getenv("PE_MCTS_GLOBAL") && atoi(getenv("PE_MCTS_GLOBAL")) != 0;
-#endif
   m->n_sims = n_simulations;
   m->max_depth = max_depth;
   m->c = c_param;
@@ -1092,7 +1087,7 @@ int pe_mcts_search(pe_mcts* m, const uint8_t* mask, int32_t* actions, int32_t* r
   int ldsp = (h->g.GG + 3) / 4 * 4;
   if ((ldsp / 4) % 2 == 0) ldsp += 4;  // odd dword stride between lanes
   const size_t lds = 64 * ((size_t)ldsp + 4 * (size_t)kRing);
-  const bool use_lds = h->g.G <= 64 && lds <= kMctsLdsMax && !m->force_global;
+  const bool use_lds = h->g.G <= 64 && lds <= kMctsLdsMax;
   if (use_lds) {
     a.cellb = m->cellb;
     a.csim = m->csim;

@@ -186,12 +186,9 @@ __device__ __forceinline__ void load_tables_cold(float* smem, const Tables* tab)
 
 // Stream the block's [valid x D] obs tile (LDS rows of stride DS) to HBM.
 // t0 / nt: this thread's index among the nt storing threads (default: the block).
-#ifndef PE_TILE_BATCH
-#define PE_TILE_BATCH 1  // obs tile store: 16-B chunks per thread read from LDS ahead of their stores (f32 20x20: 3 same, 9 slower)
-#endif
-#ifndef PE_TILE_BATCH_CODES
-#define PE_TILE_BATCH_CODES 4  // the same for the byte-coded tile (64x64: 25.6 -> 23.0 us; 2: 23.2, 6: 23.6)
-#endif
+// obs tile store: 16-B chunks per thread read from LDS ahead of their stores (f32 20x20: 3 same, 9 slower)
+constexpr int kTileBatch = 1;
+constexpr int kTileBatchCodes = 4;  // the same for the byte-coded tile (64x64: 25.6 -> 23.0 us; 2: 23.2, 6: 23.6)
 __device__ __forceinline__ void store_tile(const float* rows, float* dst, int valid, int D, int DS,
                                            int t0 = -1, int nt = 0) {
   const int total = valid * D;
@@ -200,12 +197,7 @@ __device__ __forceinline__ void store_tile(const float* rows, float* dst, int va
   if (DS == D) {
     if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
       const int n4 = total >> 2;
-      const float4* s4 = reinterpret_cast<const float4*>(rows);
       float4* d4 = reinterpret_cast<float4*>(dst);
-#if !defined(PE_OBS_STORE_ASM) && !defined(PE_OBS_STORE_NT) && !defined(PE_TEMPORAL_OBS)
-#define PE_OBS_STORE_ASM "sc1"
-#endif
-#if defined(PE_OBS_STORE_ASM)
       // the obs stream (28 MB per step at the headline batch) is written with sc1
       // (write-through; the line is dropped from the XCD's L2) so it does not evict
       // the envs' state from L2 / the Infinity Cache: plain stores 12.8 us, nt 11.4,
@@ -213,10 +205,10 @@ __device__ __forceinline__ void store_tile(const float* rows, float* dst, int va
       // compiler does not count these in vmcnt; the reset path waits explicitly.
       typedef float v4f __attribute__((ext_vector_type(4)));
       const v4f* sv = reinterpret_cast<const v4f*>(rows);
-      // PE_TILE_BATCH chunks per thread read from LDS before their stores are issued:
+      // kTileBatch chunks per thread read from LDS before their stores are issued:
       // the asm's memory clobber keeps a later LDS read below an earlier store, so
       // one chunk at a time would wait out an LDS round trip per store
-      constexpr int TB = PE_TILE_BATCH;
+      constexpr int TB = kTileBatch;
       for (int k0 = tid; k0 < n4; k0 += TB * nth) {
         v4f v[TB];
 #pragma unroll
@@ -227,18 +219,9 @@ __device__ __forceinline__ void store_tile(const float* rows, float* dst, int va
           if (k0 + b * nth < n4)
             // s_nop 1: a 128-bit store reads its data VGPRs after issue; nothing inside
             // the asm pads that hazard for hipcc's next write of them
-            asm volatile("global_store_dwordx4 %0, %1, off " PE_OBS_STORE_ASM "\n\ts_nop 1" ::"v"(d4 + k0 + b * nth),
-                         "v"(v[b])
+            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(d4 + k0 + b * nth), "v"(v[b])
                          : "memory");
       }
-#elif defined(PE_OBS_STORE_NT)
-      typedef float v4f __attribute__((ext_vector_type(4)));
-      const v4f* sv = reinterpret_cast<const v4f*>(rows);
-      v4f* dv = reinterpret_cast<v4f*>(dst);
-      for (int k = tid; k < n4; k += nth) __builtin_nontemporal_store(sv[k], &dv[k]);
-#else
-      for (int k = tid; k < n4; k += nth) d4[k] = s4[k];
-#endif
       for (int k = (n4 << 2) + tid; k < total; k += nth) dst[k] = rows[k];
     } else {
       for (int k = tid; k < total; k += nth) dst[k] = rows[k];
@@ -262,7 +245,7 @@ __device__ __forceinline__ void store_tile_codes(const uint8_t* codes, const flo
     const uint32_t* c4 = reinterpret_cast<const uint32_t*>(codes);
     typedef float v4f __attribute__((ext_vector_type(4)));
     v4f* d4 = reinterpret_cast<v4f*>(dst);
-    constexpr int TB = PE_TILE_BATCH_CODES;  // chunks per thread expanded before their stores (see store_tile)
+    constexpr int TB = kTileBatchCodes;  // chunks per thread expanded before their stores (see store_tile)
     for (int k0 = t0; k0 < n4; k0 += TB * nt) {
       uint32_t c[TB];
 #pragma unroll
@@ -278,13 +261,7 @@ __device__ __forceinline__ void store_tile_codes(const uint8_t* codes, const flo
 #pragma unroll
       for (int b = 0; b < TB; ++b)
         if (k0 + b * nt < n4) {
-#if defined(PE_OBS_STORE_ASM)
-          asm volatile("global_store_dwordx4 %0, %1, off " PE_OBS_STORE_ASM "\n\ts_nop 1" ::"v"(d4 + k0 + b * nt),
-                       "v"(v[b])
-                       : "memory");
-#else
-          d4[k0 + b * nt] = v[b];
-#endif
+          asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(d4 + k0 + b * nt), "v"(v[b]) : "memory");
         }
     }
     for (int k = (n4 << 2) + t0; k < total; k += nt) dst[k] = ctab[codes[k]];
@@ -306,47 +283,12 @@ __device__ __forceinline__ void store_tile_bytes(const uint8_t* codes, uint8_t* 
     v4u* d4 = reinterpret_cast<v4u*>(dst);
     for (int k = t0; k < n16; k += nt) {
       const v4u v = sv[k];
-      asm volatile("global_store_dwordx4 %0, %1, off " PE_OBS_STORE_ASM "\n\ts_nop 1" ::"v"(d4 + k), "v"(v) : "memory");
+      asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(d4 + k), "v"(v) : "memory");
     }
     head = n16 << 4;
   }
   for (int k = head + t0; k < total; k += nt) dst[k] = codes[k];
 }
-
-// Cache-policy operand of the buffer-store builtin: bit 4 = sc1 on gfx950 (write-through,
-// the line dropped from the XCD's L2 -- the obs stream must not evict the envs' state).
-constexpr int kBufSc1 = 16;
-constexpr int kBufRsrcWord3 = 0x00020000;  // raw buffer, 32-bit data format (range-checked)
-
-// Stream a full block's [64 x D] f32 obs tile (LDS) to dst: thread t0 of nt stores the
-// 16-B chunks t0, t0 + nt, ...; every chunk index past the tile is dropped by the
-// buffer's range check, so each wave issues exactly NI stores (a count the compiler's
-// wait for earlier loads relies on).
-template <int D, int NT>
-__device__ __forceinline__ void store_tile_buf(const float* rows, float* dst, int t0) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  constexpr int N4 = kQuadEnvs * D / 4, NI = (N4 + NT - 1) / NT;
-  static_assert((kQuadEnvs * D) % 4 == 0, "whole 16-B chunks");
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, N4 * 16, kBufRsrcWord3);
-  const v4f* sv = reinterpret_cast<const v4f*>(rows);
-  v4f v[NI];
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    const int k = t0 + NT * j;
-    v[j] = sv[k < N4 ? k : N4 - 1];
-  }
-#pragma unroll
-  for (int j = 0; j < NI; ++j) __builtin_amdgcn_raw_buffer_store_b128(v[j], rs, (t0 + NT * j) * 16, 0, kBufSc1);
-}
-
-// s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] |
-// vmcnt[5:4] at [15:14]) waiting on vmcnt alone
-constexpr int vmcnt_imm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
-constexpr int kVmcnt0 = vmcnt_imm(0);
-// the store instructions store_tile_buf issues per wave
-template <int D, int NT>
-constexpr int tile_buf_stores() { return (kQuadEnvs * D / 4 + NT - 1) / NT; }
-static_assert(vmcnt_imm(0) == 0x0F70, "s_waitcnt vmcnt(0)");
 
 // ------------------------------------------------------------------ kernels
 // Specialized fused step (compile-time C, R): two load rounds per lane, the rest
@@ -521,58 +463,13 @@ __global__ __launch_bounds__(kBlock) void pe_step_fast(StepArgs a) {
 // (The round-1 phase ablations and the round-2 timing probes -- PE_ABLATE, PE_PROBE_*,
 // PE_VIS_R1 -- were separate libraries built from this file; their results are in
 // DESIGN.md §8 and profiles/r1d_ablation.json, profiles/r2ag_*; the probes are gone.)
-#ifndef PE_GRID_R1
-#define PE_GRID_R1 1  // one-word sector kernel: the grid block in round 1 (A/B: -DPE_GRID_R1=0)
-#endif
-#ifndef PE_WAVE_ROWSTORE_MIN
-// pe_step_wave's obs row of D >= this many floats as 16-B stores (shorter: one float per
-// lane): 64x64/C64/R32 93.8 -> 90.4 us, 40x40/C48/R8 76.7 -> 75.0, but 8x8/C16/R20
-// 68.0 -> 70.2 (sc1 16-B stores: 90.8 / 76.7 / 70.4; profiles/r3x/)
-#define PE_WAVE_ROWSTORE_MIN 200
-#endif
-#ifndef PE_QUAD_TILE_BUF
-#define PE_QUAD_TILE_BUF 0  // sector kernel's f32 tile: asm sc1 stores (0); A/B: buffer stores (1, 2)
-#endif
-#ifndef PE_BT_DV
-#define PE_BT_DV 1  // the byte-coded C16R6 kernel defers its overflow writes as the f32 one (A/B: 0)
-#endif
-#ifndef PE_BT_EARLY
-#define PE_BT_EARLY 1  // the byte-coded one-word kernel loads a predicted single truncation's record early (A/B: 0)
-#endif
-#ifndef PE_REG_STAGE
-#define PE_REG_STAGE 0  // f32 kernels without the early record: a predicted single truncation's record
-                        // register-staged into LDS during round 2 (round 6 A/B: not kept)
-#endif
-#ifndef PE_RT_REG
-#define PE_RT_REG 1  // runtime sector kernel: rays from a per-wave register window (A/B: 0, the LDS-table form)
-#endif
-#ifndef PE_BT_INFO_REG
-#define PE_BT_INFO_REG 1  // byte-coded LDS-DMA kernels: the info rows register-staged by the info wave (A/B: 0)
-#endif
-#ifndef PE_GR2
-#define PE_GR2 0  // the two-word C16R6 kernel (G <= 28) loads the loader env's grid block in round 1 (A/B: not kept)
-#endif
-#ifndef PE_EARLY2
-#define PE_EARLY2 0  // one-word early-record kernels: two predicted truncations' records by waves 0 and 1 (A/B: not kept)
-#endif
-#ifndef PE_REG_STAGE_SMALL
-#define PE_REG_STAGE_SMALL 0  // ... and the 16 / 32-env small-batch shapes (A/B: 1)
-#endif
-#ifndef PE_DONE_BATCH
-#define PE_DONE_BATCH 1  // done path: the terminal / fresh obs row copies as batched reads, then writes (A/B: 0)
-#endif
-#ifndef PE_DONE_ONEWAIT
-// done path without the early record: every load (record, terminal-info rows, terminal obs)
-// issued before any store, one wait, then the stores -- vmcnt counts stores too, in order, so
-// a load consumed after a store waits for that store (A/B: 0; 2: in every kernel)
-#define PE_DONE_ONEWAIT 1
-#endif
-#ifndef PE_BT_STAGE_MIN_C
-#define PE_BT_STAGE_MIN_C 64  // byte-coded kernels stage the predicted record by LDS-DMA from this C on (A/B: 0)
-#endif
-#ifndef PE_STAGGER_GROUPS
-#define PE_STAGGER_GROUPS 4  // sector kernel: the grid's start-delay groups (A/B: -DPE_STAGGER_GROUPS=n)
-#endif
+// (The sector kernel's closed compile-time A/Bs -- the grid block in round 2, buffer tile stores,
+// the register-staged record, the two-word grid block in round 1, two early records and the
+// rest -- are recorded in DESIGN.md §8; their code is gone.)
+// byte-coded kernels stage the predicted record by LDS-DMA from this C on (see stage_ok in
+// pe_step_quad: the byte-coded C16 kernel would pay for it in round 2)
+constexpr int kBtStageMinC = 64;
+constexpr int kStaggerGroups = 4;  // sector kernel: the grid's start-delay groups
 
 // Diagnostic phase stamps (tools/stamps.py builds a SEPARATE library with
 // -DPE_STAMPS): lane 0 of every wave of the sector kernel records s_memrealtime
@@ -669,11 +566,7 @@ __device__ __forceinline__ const void* kernargs() {
 }
 
 __device__ __forceinline__ bool quad_coop(const StepArgs& a, int ndone) {
-#ifdef PE_NO_COOP
-  return false;
-#else
   return a.autoreset && ndone <= a.coop_max_done;
-#endif
 }
 
 // The single-done early record's terminal info by a second wave (round 5): the commit
@@ -681,10 +574,7 @@ __device__ __forceinline__ bool quad_coop(const StepArgs& a, int ndone) {
 // 2; at the done path the info wave reduces and stores the info while the commit wave
 // takes the record -- the info's wave reductions off the one-done block's critical path.
 // The commit wave parks the env's post-step scalars + wfix in free table words
-// (dist[24..28]) before the done barrier.  A/B: -DPE_INFO_WAVE=0.
-#ifndef PE_INFO_WAVE
-#define PE_INFO_WAVE 1
-#endif
+// (dist[24..28]) before the done barrier.
 constexpr int kQuadInfoWave = 2;  // (4-wave kernels; the slice / position wave)
 constexpr int kInfoParkF = 24;    // floats 24..28 of dist[] (dist[0..R+1] and the one-hot rows at 48.. in use)
 __device__ __forceinline__ bool el_info_hit(int64_t e_info, int64_t e0, const float* smem) {
@@ -799,7 +689,7 @@ __device__ __forceinline__ Scal dense_reset_commit(const StepArgs& a, const Tabl
 }
 
 // BT: the obs tile holds byte codes (ctab: the LDS code table), see pe_step_quad.
-// DB: the row copies batched (PE_DONE_BATCH) -- where the registers are there: rows of at most
+// DB: the row copies as batched reads, then writes -- where the registers are there: rows of at most
 // 128 values, or a path out of line (the far kernel's far_done); inlined into the C64 / runtime
 // byte-tile kernels (KD = 6) it cost their hot path (64x64/C64 24.15 -> 25.0 us, profiles/r6h/)
 template <int NW, bool ONEWORD, int KD, bool BT = false, bool DB = (KD <= 2)>  // one copy per kernel: each
@@ -810,12 +700,13 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
                                                 bool stage_info = false, int64_t e_early = -1,
                                                 const PfLoad<ONEWORD ? 1 : kCoopWPR, KD>* early = nullptr,
                                                 const Row4<ONEWORD ? 1 : kCoopWPR>* early_rows = nullptr,
-                                                int64_t e_info = -1, bool stage_reg = false, bool info_iw = false,
-                                                const float* ipark = nullptr) {
-  // stage_reg: `stage` was written by register-staged copies before the window barrier
-  // (pe_step_quad kRegStage), not by LDS-DMA: nothing to wait for.  info_iw: the env's
-  // terminal-info rows were register-staged into `stage` (after the record) by the info
-  // wave (kQuadInfoWave), which writes the terminal info beside the commit wave's reset
+                                                int64_t e_info = -1, bool stage_reg = false, bool info_iw = false) {
+  // stage_reg: always false -- `stage` written by register-staged copies, a path since removed.
+  // The parameter stays only because without it hipcc lays out the cold blocks of far_done and
+  // of the byte-tile kernels that stage by LDS-DMA differently (2-20 instructions): dropping
+  // it belongs to a change that may move instruction streams.
+  // info_iw: the env's terminal-info rows were register-staged into `stage` (after the record) by
+  // the info wave (kQuadInfoWave), which writes the terminal info beside the commit wave's reset
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const StepArgs& a = *reinterpret_cast<const StepArgs*>(ka);
   const Geo& g = a.g;
@@ -833,10 +724,12 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
   Scal s = unpack(sp);
   constexpr int MAXW = ONEWORD ? 1 : kCoopWPR;
   // the early record's terminal info is the info wave's (the kernel's kInfoW)
-  constexpr bool kIW = PE_INFO_WAVE && NW == 4 && ONEWORD && KD <= 2;
-  // loads before stores (PE_DONE_ONEWAIT): the one-word f32 kernels (1); every kernel with
-  // batched row copies (2: the multi-word and byte-tile ones measured slower)
-  constexpr bool kOneWait = PE_DONE_ONEWAIT && PE_DONE_BATCH && DB && (PE_DONE_ONEWAIT > 1 || (ONEWORD && !BT));
+  constexpr bool kIW = NW == 4 && ONEWORD && KD <= 2;
+  // done path without the early record: every load (record, terminal-info rows, terminal obs)
+  // issued before any store, one wait, then the stores -- vmcnt counts stores too, in order, so
+  // a load consumed after a store waits for that store.  The one-word f32 kernels only (the
+  // multi-word and byte-tile ones measured slower with it)
+  constexpr bool kOneWait = DB && ONEWORD && !BT;
   // the table reads of the reset / info helpers as LDS reads of ltab (pe_coop.hpp LdsTables):
   // the one-word f32 kernels (the others measured slower with them, 64x64 +0.2 us desync)
   constexpr bool kLT = ONEWORD && !BT;
@@ -967,7 +860,7 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
         } else {
           if (a.tobs) {  // (the row's reads first, then the stores: one LDS round trip, not one per 64 values)
             float* t = a.tobs + el * g.D;
-            if constexpr (PE_DONE_BATCH && DB) {
+            if constexpr (DB) {
               float tv[KD];
 #pragma unroll
               for (int j = 0; j < KD; ++j) tv[j] = lane + 64 * j < g.D ? tval(orow, lane + 64 * j) : 0.0f;
@@ -996,8 +889,7 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
           Row4<MAXW> rw;
           Scal ns;
           asm volatile("" ::: "memory");  // terminal obs read out of the row before the fresh one goes in
-          const bool took = stage ? pf_stage_take<MAXW, OT, PE_DONE_BATCH && DB ? KD : 0>(stage, g, (int)a.pf.ostride, sv.episode,
-                                                                                    rw, ns, orow, lane)
+          const bool took = stage ? pf_stage_take<MAXW, OT, DB ? KD : 0>(stage, g, (int)a.pf.ostride, sv.episode, rw, ns, orow, lane)
                                   : (a.pf.scal && take(el, sv.episode, pl, rw, ns, orow));
           if (took) {
             ns = coop_apply_reset<MAXW, kLT>(st, g, el, ns, kp, rw, lane, ltab, true);
@@ -1031,10 +923,10 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
     } else if (info_iw && a.tinfo && wv == kQuadInfoWave) {
       // the terminal info of the staged env (the block's one done env: its truncation was
       // predicted) by the info wave from its rows register-staged in round 2 and its
-      // post-step scalars parked by the commit wave (kInfoParkF; ipark: the far kernel's slot)
+      // post-step scalars parked by the commit wave (kInfoParkF)
       const uint64_t dmw = reinterpret_cast<const uint64_t*>(smem)[35];
       const int64_t el = e0 + (__ffsll((unsigned long long)dmw) - 1);
-      const float* pk = ipark ? ipark : smem + kInfoParkF;
+      const float* pk = smem + kInfoParkF;
       const uint4 spk = make_uint4((uint32_t)__builtin_amdgcn_readfirstlane(__float_as_int(pk[0])),
                                    (uint32_t)__builtin_amdgcn_readfirstlane(__float_as_int(pk[1])),
                                    (uint32_t)__builtin_amdgcn_readfirstlane(__float_as_int(pk[2])),
@@ -1139,7 +1031,7 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
         }
         if (a.tobs) {  // (the row's reads first, then the stores: one LDS round trip, not one per 64 values)
           float* t = a.tobs + el * g.D;
-          if constexpr (PE_DONE_BATCH && DB) {
+          if constexpr (DB) {
             float tv[KD];
 #pragma unroll
             for (int j = 0; j < KD; ++j) tv[j] = lane + 64 * j < g.D ? tval(orow, lane + 64 * j) : 0.0f;
@@ -1163,8 +1055,7 @@ __device__ __forceinline__ uint4 quad_done_path(const void* ka, int tile_off, in
         PfLoad<MAXW, KD> pl;
         if (a.pf.scal && !eh) coop_load_prefetched<MAXW, KD, OT>(a.pf, g, el, pl, lane);
         if (a.tinfo) {
-          // (with the info wave the single early env's rows are that wave's, not this one's;
-          // kEarly2's waves hold their env's rows themselves: e_info == e_early)
+          // (with the info wave the single early env's rows are that wave's, not this one's)
           if (eh && (!kIW || e_info == el))
             coop_info_store<MAXW, kLT>(st, g, *early_rows, sv, a.tinfo + el * PE_NINFO, lane, kw >> 1, ltab);
           else
@@ -1345,7 +1236,7 @@ __device__ __forceinline__ void quad_move_cells(QuadMove& m, const Scal& s, int 
   m.cell_n = m.nx * G + m.nyc;
 }
 
-// The compute phase of the sector kernels (pe_step_quad, pe_step_pipe), between the
+// The compute phase of the sector kernel (pe_step_quad), between the
 // window barrier and the done barrier: every wave re-derives the transition
 // (plantos_env.py:160-222) from the LDS window, marches its sector of rays and writes
 // its part of the env's obs row into the LDS tile; the commit wave (NW-1) stores the
@@ -1422,13 +1313,10 @@ __device__ __forceinline__ void quad_compute(const StepArgs& a, const uint64_t* 
       // ok word, after the LDS-form table in st.ldxy), else the LDS-table form
       const uint32_t* gt = reinterpret_cast<const uint32_t*>(st.ldxy) + Cr * ((Rr + 7) & ~7);
       const rt_cptr hdr = (rt_cptr)(gt + 4 * wv);
-#if PE_RT_REG
       if (hdr[3]) {
         quad_rays_rt_reg<OT>(lrow, hdr, (rt_cptr)(gt + 16), wv * Cr / NW, (wv + 1) * Cr / NW, Rr, lane, kc, sh, watered,
                              row, tdist);
-      } else
-#endif
-      {
+      } else {
         const uint32_t* ltab = reinterpret_cast<const uint32_t*>(reinterpret_cast<const float*>(rows) + quad_rtab_off(Cr, BT));
         quad_rays_rt<OT>(lrow, ltab, wv * Cr / NW, (wv + 1) * Cr / NW, Rr, lane, kc, sh, watered, row, tdist);
       }
@@ -1510,25 +1398,13 @@ __device__ __forceinline__ void quad_compute(const StepArgs& a, const uint64_t* 
           // The flagship's action stream moves into a cell at 15 in three of ten env-steps,
           // tools/visit_overflow_rate.py; the A/B: profiles/visit_overflow_ab.json)
           if (n < 15u) {
-#if defined(PE_PROBE_VISIDLE)  // (timing / traffic probe, wrong results: the byte into the idle slot)
-          st_wt(reinterpret_cast<uint8_t*>(vis_env(st, g, e, s.episode ^ 1u) + (int64_t)m.nx * g.NW) + b,
-                (uint8_t)(wnew >> (4 * (2 * b - m.ybv))));
-#elif defined(PE_VIS_PLAIN)  // (A/B: a write-back byte store, merged into the L2 line round 2 read)
-          *(reinterpret_cast<uint8_t*>(vis_env(st, g, e, s.episode) + (int64_t)m.nx * g.NW) + b) =
-              (uint8_t)(wnew >> (4 * (2 * b - m.ybv)));
-#else
-          st_wt(reinterpret_cast<uint8_t*>(vis_env(st, g, e, s.episode) + (int64_t)m.nx * g.NW) + b,
-                (uint8_t)(wnew >> (4 * (2 * b - m.ybv))));
-#endif
+            st_wt(reinterpret_cast<uint8_t*>(vis_env(st, g, e, s.episode) + (int64_t)m.nx * g.NW) + b,
+                  (uint8_t)(wnew >> (4 * (2 * b - m.ybv))));
           }
-#if defined(PE_PROBE_NOVX)  // (timing probe, counts past 15 wrong: no overflow bookkeeping at all)
-          if constexpr (!DV) visit_bump_exact(st, g, e, m.cell_n, n);
-#else
           if constexpr (DV)
             np = vx_pending(m.cell_n, n);
           else
             visit_bump_exact(st, g, e, m.cell_n, n);
-#endif
           if (s.flags & F_EXPL_BITMAP) {
             uint32_t* ep_o = st.expl + e * g.estride + (m.cell_o >> 5);
             uint32_t* ep_n = st.expl + e * g.estride + (m.cell_n >> 5);
@@ -1551,22 +1427,18 @@ __device__ __forceinline__ void quad_compute(const StepArgs& a, const uint64_t* 
         }
       }
       ret += rew;
-#if !defined(PE_PROBE_NOOUT)
       st_wt(a.reward + e, (float)rew);
       st_wt(a.term + e, (uint8_t)term);
       st_wt(a.trunc + e, (uint8_t)trunc);
-#endif
       if (done) {  // Monitor's episode return / length of the ended episode
         if (a.ep_ret_out) st_wt(a.ep_ret_out + e, ret);
         if (a.ep_len_out) st_wt(a.ep_len_out + e, (int32_t)s.step);
       }
       // an env about to be auto-reset: its reset path stores the new episode's scalars
-#if !defined(PE_PROBE_NOSCAL)
       if (!(done && a.autoreset && !st.cur)) {
         st_wt(st.ep_ret + e, ret);
         st_wt(st.scal + e, pack(s));
       }
-#endif
       if constexpr (DV) {
         if (vp0 | np) st_wt(st.vpend + e, np);
       }
@@ -1580,12 +1452,8 @@ __device__ __forceinline__ void quad_compute(const StepArgs& a, const uint64_t* 
 // EPB: envs per workgroup (64; 16 / 32 for small batches: more workgroups, so that
 // a batch of a few thousand envs spreads over every CU -- lanes >= EPB idle).  The
 // LDS layout keeps the 64-env stride LS whatever EPB.
-// GR2 (round 6): two-word rows (WPR == 2) of a grid small enough (G <= kGr2MaxG: 25x25, the
-// training scripts' grid) that the loader env's whole block comes in round 1, as the one-word
-// kernel's (kGridR1): round 2 then holds only the visit rows.
-constexpr int kGr2MaxG = 28;
-template <int C, int R, bool ONEWORD, int NW, bool BT = false, int EPB = kQuadEnvs, bool GR2 = false>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) void pe_step_quad(StepArgs a) {  // NW=8: <= 80 SGPRs (small-batch EPB: one workgroup per CU, no cap); NW=4: <= 128 VGPRs (4 workgroups per CU: G=25 13.1 -> 10.5 us; 1-word C16: 122 -> 104 VGPRs)
+template <int C, int R, bool ONEWORD, int NW, bool BT = false, int EPB = kQuadEnvs>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 4) void pe_step_quad(StepArgs a) {  // NW=8 (the 16-env small-batch shape: one workgroup per CU, no cap); NW=4: <= 128 VGPRs (4 workgroups per CU: G=25 13.1 -> 10.5 us; 1-word C16: 122 -> 104 VGPRs)
   // C == 0 (R == 0): the runtime-(C, R) sector kernel (quad_rays_rt): C, R from the
   // geometry (up to kRtCMax -- kRtCMaxBT with the byte-coded tile -- / kRtRMax), the LDS
   // layout sized at run time
@@ -1599,6 +1467,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // after the tile (+ code table): RT's probe table (quad_rtab_off), then the staging region
   const int tail_off = tile_off + quad_rtab_off(Cr, BT);
   static_assert(EPB == 16 || EPB == 32 || EPB == 64, "envs per workgroup");
+  static_assert(NW == 4 || (NW == 8 && EPB == 16), "8 waves: the 16-env small-batch shape only");
   static_assert(!BT || EPB == kQuadEnvs, "the byte-coded kernel's LDS-DMA staging predicts over all 64 lanes");
 
   static_assert(RT || C >= NW, "every wave owns a sector of at least one ray");
@@ -1627,7 +1496,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // each load instruction reads LT consecutive rows of 64/LT envs instead of one row of 64.
   PE_STAMP(0);
   if (a.stagger) {  // de-phase the resident workgroups of a CU (speed only)
-    const int q = (int)(blockIdx.x * PE_STAGGER_GROUPS / gridDim.x);
+    const int q = (int)(blockIdx.x * kStaggerGroups / gridDim.x);
     for (int i = 0; i < q * a.stagger; ++i) __builtin_amdgcn_s_sleep(8);
   }
   constexpr int LT = NW * (LS / EPB);
@@ -1648,14 +1517,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // only -- measured faster there (9.66 -> 9.52 us), slower in the constructor default's
   // multi-word C10R2 kernel (8.22 -> 8.69) and the 16-env small-batch shape (4.44 -> 4.61),
   // profiles/r4q/, r4v/
-  // (round 5: the byte-coded twin of the headline kernel too -- config 5's codes step, A/B
-  // PE_BT_DV=0)
-  constexpr bool DV = C == 16 && R == 6 && ONEWORD && NW == 4 && (PE_BT_DV || !BT) && EPB == kQuadEnvs;
-#if defined(PE_PROBE_NOVX)  // (timing probe: the DV kernels without their vpend load, apply and store)
-  const uint32_t vp0 = 0u;
-#else
+  // (round 5: the byte-coded twin of the headline kernel too -- config 5's codes step)
+  constexpr bool DV = C == 16 && R == 6 && ONEWORD && NW == 4 && EPB == kQuadEnvs;
   const uint32_t vp0 = DV ? st.vpend[wv == CW || wv == 0 ? ec : 0] : 0u;  // (wave 0 applies, CW stores)
-#endif
   // (Tried: the loader env's position by a bpermute from lane le of the wave instead of
   // this load -- 64x64 24.5 -> 25.2 us, 25x25 desync +0.4 us, the headline unchanged;
   // profiles/r3m_ab_*.jsonl.)
@@ -1663,12 +1527,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // one-word rows (G <= 20): the loader env's whole grid block (gstride / 2 <= 10
   // 16-B units, contiguous, 3 per loader thread) comes in round 1 -- its address does
   // not depend on the position -- and only the visit rows are left for round 2
-  static_assert(!GR2 || (!ONEWORD && !RT && NW == 4 && EPB == kQuadEnvs), "GR2: the two-word 64-env kernel");
-  constexpr int JG1 = GR2 ? (kGr2MaxG + LT - 1) / LT : (10 + LT - 1) / LT;  // gstride / 2 <= 10 16-B units (one-word:
-                                                                            // NW == 4, G <= 20); GR2: G <= kGr2MaxG rows
-  constexpr bool kGridR1 = (ONEWORD && PE_GRID_R1) || GR2;
-  uint4 qg1[kGridR1 ? JG1 : 1];
-  if constexpr (kGridR1) {
+  constexpr int JG1 = (10 + LT - 1) / LT;  // gstride / 2 <= 10 16-B units (one-word: NW == 4, G <= 20)
+  uint4 qg1[ONEWORD ? JG1 : 1];
+  if constexpr (ONEWORD) {
     const uint4* lgq = reinterpret_cast<const uint4*>(st.grid + elc * g.gstride);
     const int nq = (int)(g.gstride >> 1);
 #pragma unroll
@@ -1710,9 +1571,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // around a possibly outstanding LDS-DMA (a vmcnt(0) at the next use of any load
   // result) serialize round 2 in every block (9.39 -> 10.0 us, desync 11.52 -> 12.29).
   float* stage = smem + tail_off + (RT ? quad_rtab_floats(Cr, Rr) : 0);
-  // (C >= PE_BT_STAGE_MIN_C only: the byte-coded C16 kernel -- config 5's codes step --
+  // (C >= kBtStageMinC only: the byte-coded C16 kernel -- config 5's codes step --
   // pays the same round-2 serialization as the f32 one would)
-  const bool stage_ok = BT && CM >= PE_BT_STAGE_MIN_C && a.pf.scal && quad_coop(a, 1) &&
+  const bool stage_ok = BT && CM >= kBtStageMinC && a.pf.scal && quad_coop(a, 1) &&
                         e0 + EPB <= a.n;  // full block: every lane live
   const bool stage_info = !st.cur && a.tinfo && pf_stage_info_fits(g.G, g.WPR, (int)a.pf.ostride);
   // (issued right after round 2's own loads: hipcc drains every memory op in flight
@@ -1730,7 +1591,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // so that the info wave writes the terminal info beside the commit wave's reset instead
   // of the commit wave loading them after the done barrier (a round trip on its path)
   const int ng_s = pf_grid_units(g.G, g.WPR);
-  const bool info_reg = BT && PE_BT_INFO_REG && stage_ok && !stage_info && !st.cur && a.tinfo != nullptr && ng_s <= 128;
+  const bool info_reg = BT && stage_ok && !stage_info && !st.cur && a.tinfo != nullptr && ng_s <= 128;
   uint4 iq0 = make_uint4(0u, 0u, 0u, 0u), iq1 = iq0;
   auto stage_issue = [&]() {
     if (BT && wv == CW && npred == 1)
@@ -1757,37 +1618,25 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // spilled with it -- 25x25 desynchronized 14.0 -> 14.6 us -- and the 16-env shape of
   // small batches lost 2-5 % synchronized; profiles/r3c_ab_early_*.jsonl)
   // (round 5: the byte-coded one-word kernel too -- config 5's codes step; the record's
-  // codes come in as 4-code words; A/B: -DPE_BT_EARLY=0)
-  constexpr bool kEarlyRec = (!BT || PE_BT_EARLY) && ONEWORD && EPB == LS && KDQ <= 2;
+  // codes come in as 4-code words)
+  constexpr bool kEarlyRec = ONEWORD && EPB == LS && KDQ <= 2;
   PfLoad<MAXWQ, KDQ> epl;
   Row4<MAXWQ> eir;
   int64_t e_early = -1, e_info = -1;
-  constexpr bool kInfoW = kEarlyRec && PE_INFO_WAVE && NW == 4;
+  constexpr bool kInfoW = kEarlyRec && NW == 4;
   static_assert(!kInfoW || (RM + 2 <= kInfoParkF && kInfoParkF + 5 <= kOneHotF), "info park words inside dist[]");
   if constexpr (kEarlyRec) {
     // (the commit wave only, for a block with exactly one: records for up to one
     // predicted env per wave took the desynchronized step 11.16 -> 11.06 us but the
     // synchronized one 9.42 -> 9.49, profiles/r3g_ab_*.jsonl; round 5: the env's rows
     // for its terminal info by the info wave)
-    // (round 6, kEarly2: a block with exactly TWO predicted truncations -- ~2 of the 1024
-    // blocks of a desynchronized 65536-env step, which the one-done blocks' early record left
-    // as the step's last blocks -- has waves 0 and 1 load one env's record and rows each:
-    // the cooperative path hands the k-th done env to wave k, so each finds its own)
-    constexpr bool kEarly2 = PE_EARLY2 && NW == 4;
-    if ((wv == CW || (kInfoW && wv == kQuadInfoWave) || (kEarly2 && wv < 2)) && a.pf.scal && a.autoreset && !st.cur) {
+    if ((wv == CW || (kInfoW && wv == kQuadInfoWave)) && a.pf.scal && a.autoreset && !st.cur) {
       const uint64_t pmk = __ballot(live && s.step + 1 >= rl.max_steps);
       const uint32_t plo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pmk),
                      phi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pmk >> 32));
       const uint64_t pmu = (uint64_t)plo | ((uint64_t)phi << 32);
       const int npk = __popcll(pmu);
-      if (kEarly2 && npk == 2 && wv < 2) {
-        const uint64_t lowb = pmu & (0ull - pmu);
-        const int64_t ep = e0 + (__ffsll((unsigned long long)(wv == 0 ? lowb : (pmu ^ lowb))) - 1);
-        e_early = ep;
-        e_info = ep;
-        coop_load_prefetched<MAXWQ, KDQ, OT>(a.pf, g, ep, epl, lane);
-        eir = coop_info_rows<MAXWQ>(st, g, ep, lane);
-      } else if (npk == 1 && wv >= 2) {
+      if (npk == 1) {
         const int64_t ep = e0 + (__ffsll((unsigned long long)pmu) - 1);
         if (wv == CW) {
           e_early = ep;
@@ -1800,58 +1649,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
       }
     }
   }
-  // Register-staged record (round 6; the f32 kernels that have neither the early record
-  // nor LDS-DMA staging: the multi-word rows -- 25x25, 21x21 -- the runtime-(C, R) f32
-  // kernel and the 16 / 32-env small-batch shapes).  A block whose ONLY env to truncate
-  // this step is known from its step count (:177) has the commit wave load that env's
-  // prefetched record -- scalars, grid rows, obs row: one 16-B unit per lane, the layout
-  // of pf_stage_issue -- and the info wave the env's current grid rows, right after round
-  // 2's loads; both are written into the LDS staging region after round 2's LDS writes,
-  // so they hold 4 VGPRs through round 2 only (the early record's registers live across
-  // the compute phase spilled the multi-word kernel, at its 128-VGPR cap), and the single-
-  // done path makes no memory round trip: the commit wave takes the staged record, the
-  // info wave writes the terminal info from the staged rows beside it.
-  // (not the 16 / 32-env small-batch shapes: 4096 envs synchronized 4.43 -> 4.62 us for
-  // desynchronized 6.38 -> 6.30, profiles/r6c/)
-  constexpr bool kRegStage =
-      PE_REG_STAGE && !kEarlyRec && !BT && NW > kQuadInfoWave && (EPB == kQuadEnvs || PE_REG_STAGE_SMALL);
-  // (the staging outcome goes to LDS -- kRsFlagF, written by the commit wave every launch --
-  // and the done env's scalars are parked after the compute phase: no SGPRs live across it)
-  constexpr int kRsFlagF = kInfoParkF + 5;
-  static_assert(!(kRegStage || BT) || (RM + 2 <= kInfoParkF && kRsFlagF + 1 <= kOneHotF), "info park words inside dist[]");
-  bool rs_on = false, rs_info = false;  // (wave-uniform; identical in the commit and the info wave)
-  int64_t e_rs = -1;
-  uint4 rq = make_uint4(0u, 0u, 0u, 0u);
-  int rs_u = 0, rs_n = 0;  // this lane's staging unit, the wave's unit count
-  if constexpr (kRegStage) {
-    if ((wv == CW || wv == kQuadInfoWave) && a.pf.scal && a.autoreset && !st.cur && quad_coop(a, 1)) {
-      const uint64_t pmk = __ballot(live && s.step + 1 >= rl.max_steps);
-      const uint64_t pmu = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pmk) |
-                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pmk >> 32)) << 32);
-      const int ng = pf_grid_units(g.G, g.WPR), no = (int)a.pf.ostride / 16;
-      if (__popcll(pmu) == 1 && 1 + ng + no <= 64) {
-        rs_on = true;
-        rs_info = a.tinfo != nullptr;
-        e_rs = e0 + (__ffsll((unsigned long long)pmu) - 1);
-        rs_n = wv == CW ? 1 + ng + no : (rs_info ? ng : 0);
-        rs_u = (wv == CW ? 0 : 1 + ng + no) + (lane < rs_n ? lane : rs_n - 1);
-      }
-    }
-  }
-  auto rs_issue = [&]() {
-    if (kRegStage && rs_n > 0) {
-      const int ng = pf_grid_units(g.G, g.WPR);
-      const int u = rs_u;
-      const uint4* src;
-      if (wv == CW)
-        src = u == 0 ? reinterpret_cast<const uint4*>(a.pf.scal + e_rs)
-                     : (u <= ng ? reinterpret_cast<const uint4*>(a.pf.grid + e_rs * g.gstride) + (u - 1)
-                                : reinterpret_cast<const uint4*>(pf_obs_row(a.pf, e_rs)) + (u - 1 - ng));
-      else
-        src = reinterpret_cast<const uint4*>(st.grid + e_rs * g.gstride) + (u - (1 + ng + (int)a.pf.ostride / 16));
-      rq = *src;
-    }
-  };
+  static_assert(!BT || (RM + 2 <= kInfoParkF && kInfoParkF + 5 <= kOneHotF), "info park words inside dist[]");
   // ---- round 2: window rows of env le -> LDS [row][env] (loader role)
   uint32_t eo = 0u, en = 0u;
   if (llive) {
@@ -1863,19 +1661,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
     // compiler issues all of them back to back and waits once -- with the range
     // tests around the loads it waited after each (one memory round trip per row).
     if constexpr (ONEWORD) {
-      // row pairs (16 B, aligned: env blocks are 16-B aligned, pairs start on even rows)
-      const int ps = base & ~1;
-      constexpr int NP = (NR + 2) / 2, JG = kGridR1 ? 1 : (NP + LT - 1) / LT, JV = (NV + LT - 1) / LT;
-      const int gmax = g.G - 2 > 0 ? g.G - 2 : 0;
-      uint4 qg[JG], qv[JV];
-      if constexpr (!kGridR1) {
-#pragma unroll
-        for (int j = 0; j < JG; ++j) {
-          const int ra = ps + 2 * (sub + LT * j);
-          const int rc = ra < 0 ? 0 : (ra > gmax ? gmax : ra);
-          qg[j] = *reinterpret_cast<const uint4*>(lgb + rc);
-        }
-      }
+      // (the grid block came with round 1: qg1, row pairs of 16 B)
+      constexpr int JV = (NV + LT - 1) / LT;
+      uint4 qv[JV];
       const uint32_t* lvb = vis_env(st, g, el, lw.w);  // (lw.w: the loader env's episode)
       {
 #pragma unroll
@@ -1887,41 +1675,22 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
         }
       }
       stage_issue();
-      rs_issue();  // (after round 2's loads: their waits stay as they were)
-      if constexpr (kGridR1) {
-        // the block's rows (pairs 2q, 2q+1) inside the window, then the off-map rows
-        const int nq = (int)(g.gstride >> 1);
+      // the block's rows (pairs 2q, 2q+1) inside the window, then the off-map rows
+      const int nq = (int)(g.gstride >> 1);
 #pragma unroll
-        for (int j = 0; j < JG1; ++j) {
-          const int q = sub + LT * j, ka = 2 * q - base;
-          if (q < nq) {
-            const uint64_t lo = (uint64_t)qg1[j].x | ((uint64_t)qg1[j].y << 32);
-            const uint64_t hi = (uint64_t)qg1[j].z | ((uint64_t)qg1[j].w << 32);
-            if (ka >= 0 && ka < NRL) lrow[ka * LS + le] = lo;
-            if (ka + 1 >= 0 && ka + 1 < NRL && 2 * q + 1 < g.G) lrow[(ka + 1) * LS + le] = hi;
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < (NR + LT - 1) / LT; ++j) {
-          const int k = sub + LT * j, xr = base + k;
-          if (k < NRL && (xr < 0 || xr >= g.G)) lrow[k * LS + le] = kEven64;  // off-map rows: obstacles
+      for (int j = 0; j < JG1; ++j) {
+        const int q = sub + LT * j, ka = 2 * q - base;
+        if (q < nq) {
+          const uint64_t lo = (uint64_t)qg1[j].x | ((uint64_t)qg1[j].y << 32);
+          const uint64_t hi = (uint64_t)qg1[j].z | ((uint64_t)qg1[j].w << 32);
+          if (ka >= 0 && ka < NRL) lrow[ka * LS + le] = lo;
+          if (ka + 1 >= 0 && ka + 1 < NRL && 2 * q + 1 < g.G) lrow[(ka + 1) * LS + le] = hi;
         }
       }
 #pragma unroll
-      for (int j = 0; j < JG; ++j) {
-        const int pp = sub + LT * j;
-        if (!kGridR1 && pp < NP) {
-          const int ra = ps + 2 * pp;
-          const int rc = ra < 0 ? 0 : (ra > gmax ? gmax : ra);
-          const uint64_t lo = (uint64_t)qg[j].x | ((uint64_t)qg[j].y << 32);
-          const uint64_t hi = (uint64_t)qg[j].z | ((uint64_t)qg[j].w << 32);
-          // off-map rows: obstacles
-          const uint64_t va = (ra >= 0 && ra < g.G) ? (ra == rc ? lo : hi) : kEven64;
-          const uint64_t vb2 = (ra + 1 >= 0 && ra + 1 < g.G) ? (ra + 1 == rc ? lo : hi) : kEven64;
-          const int ka = ra - base;
-          if (ka >= 0 && ka < NRL) lrow[ka * LS + le] = va;
-          if (ka + 1 >= 0 && ka + 1 < NRL) lrow[(ka + 1) * LS + le] = vb2;
-        }
+      for (int j = 0; j < (NR + LT - 1) / LT; ++j) {
+        const int k = sub + LT * j, xr = base + k;
+        if (k < NRL && (xr < 0 || xr >= g.G)) lrow[k * LS + le] = kEven64;  // off-map rows: obstacles
       }
       // visit rows: one 16-B row per load, funnel-shifted to ybv
       const int lybv = ly > 0 ? ly - 1 : 0;
@@ -1944,12 +1713,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
       const int lyb = ly > 0 ? ly - 1 : 0;
       const int w0 = (2 * lyb) >> 6, o = (2 * lyb) & 63;
       const int w1 = w0 + 1 < g.WPR ? w0 + 1 : w0;  // in bounds; its word is dropped when w0 is the last
-      constexpr int JG = GR2 ? 1 : (NR + LT - 1) / LT, JV = (NV + LT - 1) / LT;
+      constexpr int JG = (NR + LT - 1) / LT, JV = (NV + LT - 1) / LT;
       uint64_t glo[JG], ghi[JG];
       uint32_t vlo[JV], vhi[JV];
-      if constexpr (GR2) {
-        // (the rows came with round 1: qg1, unit q = grid row q)
-      } else if (g.WPR == 2) {  // (G <= 52, e.g. the training scripts' 25x25) a row is one aligned 16-B load
+      if (g.WPR == 2) {  // (G <= 52, e.g. the training scripts' 25x25) a row is one aligned 16-B load
 #pragma unroll
         for (int j = 0; j < JG; ++j) {
           const int xr = base + sub + LT * j;
@@ -1980,30 +1747,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
         vhi[j] = vb[(int64_t)xc * g.NW + 1];  // vw + 1 < NW always (one spare word per row)
       }
       stage_issue();
-      rs_issue();  // (after round 2's loads: their waits stay as they were)
-      if constexpr (GR2) {
-        // the loader env's rows inside the window, funnel-shifted to padded column yb, then
-        // the off-map rows (obstacles)
-#pragma unroll
-        for (int j = 0; j < JG1; ++j) {
-          const int q = sub + LT * j, k = q - base;
-          if (q < g.G && k >= 0 && k < NRL) {
-            const uint64_t lo64 = (uint64_t)qg1[j].x | ((uint64_t)qg1[j].y << 32);
-            const uint64_t hi64 = (uint64_t)qg1[j].z | ((uint64_t)qg1[j].w << 32);
-            const uint64_t lo = w0 ? hi64 : lo64, hi = w0 ? 0ull : hi64;
-            lrow[k * LS + le] = o ? ((lo >> o) | (hi << (64 - o))) : lo;
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < (NR + LT - 1) / LT; ++j) {
-          const int k = sub + LT * j, xr = base + k;
-          if (k < NRL && (xr < 0 || xr >= g.G)) lrow[k * LS + le] = kEven64;  // off-map rows: obstacles
-        }
-      }
 #pragma unroll
       for (int j = 0; j < JG; ++j) {
         const int k = sub + LT * j;
-        if (!GR2 && k < NRL) {
+        if (k < NRL) {
           const int xr = base + k;
           uint64_t v = kEven64;  // off-map rows read as obstacles
           if (xr >= 0 && xr < g.G) {
@@ -2027,13 +1774,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
         }
       }
     }
-  } else {
-    rs_issue();  // (a lane whose loader env is past the batch end: its staging unit all the same)
   }
-  // the register-staged units into the LDS staging region (after round 2's LDS writes:
-  // the wait for them is the last of the round)
-  if (kRegStage && rs_n > 0 && lane < rs_n) reinterpret_cast<uint4*>(stage)[rs_u] = rq;
-  if (kRegStage && wv == CW && lane == 0) smem[kRsFlagF] = __int_as_float((int)rs_on | ((int)rs_info << 1));
+  // the info wave's register-staged rows into the LDS staging region (after round 2's LDS
+  // writes: the wait for them is the last of the round)
   if (BT && info_reg && wv == kQuadInfoWave && npred == 1) {
     uint4* d = reinterpret_cast<uint4*>(stage) + 1 + ng_s + (int)a.pf.ostride / 16;
     if (lane < ng_s) d[lane] = iq0;
@@ -2057,8 +1800,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   // (not asm), so that the done path's first use of it carries none -- otherwise it
   // waits vmcnt(0) there, i.e. for the commit's stores too (in-order counter)
   if constexpr (kEarlyRec) {
-    if (wv == CW || (kInfoW && wv == kQuadInfoWave) || (PE_EARLY2 && NW == 4 && wv < 2))
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    if (wv == CW || (kInfoW && wv == kQuadInfoWave)) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   }
   PE_STAMP(2);
   __syncthreads();
@@ -2094,8 +1836,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
       smem[kInfoParkF + 4] = __int_as_float((int)wfix);
     }
   }
-  if constexpr (kRegStage || (BT && !kEarlyRec && NW > kQuadInfoWave)) {  // a block's one done env's post-step
-                                                                           // scalars for the info wave (as kInfoW)
+  if constexpr (BT && !kEarlyRec && NW > kQuadInfoWave) {  // a block's one done env's post-step scalars for the
+                                                            // info wave (as kInfoW)
     if (wv == CW) {
       const uint64_t dm1 = __ballot(done);
       if (__popcll(dm1) == 1 && done) {
@@ -2140,13 +1882,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
   const int64_t valid = a.n - e0 < EPB ? a.n - e0 : EPB;
   if (__builtin_expect(any_done, 0)) {  // cold: laid out after the hot path
     const bool staged = stage_ok && npred == 1 && ndone == 1;  // then the done env is the predicted one
-    // (register-staged: the single done env is the predicted one likewise)
-    const int rsf = kRegStage ? __builtin_amdgcn_readfirstlane(__float_as_int(smem[kRsFlagF])) : 0;
-    const bool rstaged = kRegStage && (rsf & 1) && ndone == 1;
     const uint4 ns = quad_done_path<NW, ONEWORD, (5 * CM + 27 + 63) / 64, BT>(
         kernargs(), tile_off, Cr, Rr, lane, wv, CW, e0, done, pack(s), ret, ndone, wfix, ctab,
-        (staged || rstaged) ? stage : nullptr, (staged && stage_info) || (rstaged && (rsf & 2)), e_early, &epl, &eir,
-        e_info, rstaged, (rstaged && (rsf & 2)) || (staged && info_reg));
+        staged ? stage : nullptr, staged && stage_info, e_early, &epl, &eir, e_info, false, staged && info_reg);
     s = unpack(ns);
   }
   // the obs tile goes out through the waves other than the commit wave: its state
@@ -2163,22 +1901,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
     } else
       store_tile(rows, a.obs + e0 * g.D, (int)valid, g.D, g.D);
   } else {
-#if PE_QUAD_TILE_BUF
-    // A/B (debug builds): the f32 tile as compiler-counted buffer stores (pe_pipe.hpp's
-    // form), by the non-commit waves (1) or by every wave (2)
-    constexpr int kTB = PE_QUAD_TILE_BUF;
-    if constexpr (!BT && !RT && EPB == kQuadEnvs) {
-      float* dst = a.obs + e0 * g.D;
-      if (valid == LS && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-        if (kTB == 2)
-          store_tile_buf<5 * C + 27, 64 * NW>(rows, dst, (int)threadIdx.x);
-        else if (wv != CW)
-          store_tile_buf<5 * C + 27, 64 * (NW - 1)>(rows, dst, (int)threadIdx.x);
-      } else if (wv != CW) {
-        store_tile(rows, dst, (int)valid, g.D, g.D, (int)threadIdx.x, 64 * (NW - 1));
-      }
-    } else
-#endif
     if (wv != CW) {
       if constexpr (BT) {
         if (a.obs_codes)
@@ -2214,10 +1936,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (EPB < kQuadEnvs ? 2 : 8) : 4) v
 }
 
 #include "pe_far.hpp"  // pe_step_far<C, R>: the sector kernel of long LIDAR ranges (R > 14)
-
-#ifdef PE_DEBUG_KNOBS  // the persistent pipelined kernel: a debug-build A/B only (measured slower)
-#include "../../tools/diag/pe_pipe.hpp"  // (the closed A/B kernel lives with the diagnostics)
-#endif
 
 // ---------------------------------------------------------------- pe_step_wave
 // The fused step for every geometry without a compile-time sector kernel (any
@@ -2320,11 +2038,15 @@ __device__ __attribute__((noinline)) void wave_done(const StepArgs& a, int64_t e
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 }
 
+// waves per SIMD of the multi-word variant: 8 spills ~130 B/lane yet beats 7 / 6 (64x64/R=32:
+// 110.1 / 117.3 / 112.8 us)
+constexpr int kWaveWpe4 = 8;
+// pe_step_wave's obs row of D >= this many floats as 16-B stores (shorter: one float per
+// lane): 64x64/C64/R32 93.8 -> 90.4 us, 40x40/C48/R8 76.7 -> 75.0, but 8x8/C16/R20
+// 68.0 -> 70.2 (sc1 16-B stores: 90.8 / 76.7 / 70.4; profiles/r3x/)
+constexpr int kWaveRowstoreMin = 200;
 template <int MAXW, bool ALN>  // the cooperative reset's row words (1 or kCoopWPR); rover-aligned rays
-#ifndef PE_WAVE_WPE4  // waves per SIMD of the multi-word variant (A/B builds only): 8 spills
-#define PE_WAVE_WPE4 8  // ~130 B/lane yet beats 7 / 6 (64x64/R=32: 110.1 / 117.3 / 112.8 us)
-#endif
-__global__ __launch_bounds__(64 * kWaveEnvs) __attribute__((amdgpu_waves_per_eu(MAXW == 1 ? 8 : PE_WAVE_WPE4))) void pe_step_wave(StepArgs a) {  // <= 64 VGPRs at 8
+__global__ __launch_bounds__(64 * kWaveEnvs) __attribute__((amdgpu_waves_per_eu(MAXW == 1 ? 8 : kWaveWpe4))) void pe_step_wave(StepArgs a) {  // <= 64 VGPRs at 8
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const Geo& g = a.g;
   const Rules& rl = a.rl;
@@ -2674,7 +2396,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) __attribute__((amdgpu_waves_per_eu(
   const int n4 = (D - hd) >> 2;
   // (rover-aligned kernels only: in the other one its registers made the SGPRs spill, and
   // none of its geometries benched has rows that long)
-  if (ALN && D >= PE_WAVE_ROWSTORE_MIN && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0) {
+  if (ALN && D >= kWaveRowstoreMin && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0) {
     typedef float v4f __attribute__((ext_vector_type(4)));
     for (int k = lane; k < n4; k += 64) {
       const float* sr = row + hd + 4 * k;
@@ -3090,13 +2812,7 @@ __global__ void pe_synth_kernel(int n, uint64_t seed, uint32_t env_off, uint32_t
 // f32 | terminated | truncated, block b at src + b * stride) -> contiguous f32 obs
 // (+ the other outputs).  Grid: (x: 16-B output chunks, y: block); one u32 of 4 codes
 // per thread through the LDS code table, one 16-B store.
-#ifndef PE_EXPAND_PER
-#define PE_EXPAND_PER 4
-#endif
-#ifndef PE_EXPAND_SC1
-#define PE_EXPAND_SC1 1  // write-through expanded obs (expansion 7.85 -> 5.93 us, gather leg 20.45 -> 19.4; A/B: 0)
-#endif
-constexpr int kExpandPer = PE_EXPAND_PER;  // 4-code groups per thread (the table build amortized over them)
+constexpr int kExpandPer = 4;  // 4-code groups per thread (the table build amortized over them)
 __global__ __launch_bounds__(256) void pe_expand_codes_kernel(const Tables* tab, int R, int G, int D, int rows,
                                                               const uint8_t* src, int64_t stride, float* obs,
                                                               float* rew, uint8_t* te, uint8_t* tr) {
@@ -3129,11 +2845,9 @@ __global__ __launch_bounds__(256) void pe_expand_codes_kernel(const Tables* tab,
         v.y = ctab[(c[j] >> 8) & 255u];
         v.z = ctab[(c[j] >> 16) & 255u];
         v.w = ctab[c[j] >> 24];
-#if PE_EXPAND_SC1  // the expanded obs stream write-through, as the step kernels' tile stores
+        // the expanded obs stream write-through, as the step kernels' tile stores (expansion
+        // 7.85 -> 5.93 us, gather leg 20.45 -> 19.4)
         asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ob + 4 * k), "v"(v) : "memory");
-#else
-        *reinterpret_cast<v4f*>(ob + 4 * k) = v;
-#endif
       }
     }
   } else {
@@ -3233,11 +2947,6 @@ size_t lds_bytes(const Geo& g) {
 // (same-box A/B, profiles/r3b_ab_epb*.jsonl: 4096 envs 5.06 -> 4.55 us with 16-env
 // workgroups, 8192: 16 ~ 32, 16384: 32 best, 32768: 32 ~ 64)
 constexpr int kSmallBatch16 = 8192, kSmallBatch32 = 32768, kSmallBatch8W = 4096;
-// The persistent pipelined kernel (pe_pipe.hpp) is compiled into debug builds only
-// (PE_PIPE=P workgroups per CU): measured slower than pe_step_quad at every residency
-// (same box, 65536 envs, profiles/r4b/ab_pipe.jsonl: quad 9.63 us, pipe P2 12.14, P3
-// 11.71, P4 11.54; desynchronized 13.0 vs 23.5-25.4): at 2-3 workgroups per CU the
-// compute phase runs at 2-3 waves per SIMD, and P4 spills (128 VGPRs + 47 spilled).
 
 enum Variant {
   V_GENERIC = 0, V_C16R6_1W = 1, V_C16R6 = 2, V_C64R6 = 3,
@@ -3256,12 +2965,11 @@ size_t quad_lds_bytes(const Geo& g, bool codes, bool rt) {
                      (rt ? (size_t)quad_rtab_floats(g.C, g.R) : 0);  // (+ the runtime kernel's probe table)
   // + the single-done record's LDS-DMA staging region (pe_coop.hpp pf_stage_issue)
   size_t stage = (size_t)pf_stage_bytes(g.G, g.WPR, (int)pf_ostride(g, codes));
-  // (f32 kernels: the register-staged record and, beside it, the info wave's rows --
-  // pe_step_quad kRegStage stages whenever the record fits one unit per lane)
+  // (f32 kernels: slack left from a removed staging path; shrinking it moves occupancy -- a measured change)
   const int ng = pf_grid_units(g.G, g.WPR), no = (int)pf_ostride(g, codes) / 16;
   if (!codes && 1 + ng + no <= 64) stage = std::max(stage, (size_t)((1 + 2 * ng + no + 63) / 64) * 1024);
   // (byte-coded kernels that stage by LDS-DMA: the record, then the info wave's rows)
-  if (codes && (rt || g.C >= PE_BT_STAGE_MIN_C) && ng <= 128)
+  if (codes && (rt || g.C >= kBtStageMinC) && ng <= 128)
     stage = std::max(stage, (size_t)((1 + 2 * ng + no + 63) / 64) * 1024);
   if (codes)  // byte tile + code table (quad_ctab_off)
     return sizeof(float) * (off + (size_t)((kQuadEnvs * g.D + 15) / 16) * 4 + 256) + stage;
@@ -3277,29 +2985,7 @@ size_t step_lds_bytes(const Geo& g, int variant, bool codes) {
   return quad_lds_bytes(g, codes, variant >= V_QUAD_RT_1W);
 }
 
-#ifdef PE_DEBUG_KNOBS
-// the persistent pipelined kernel's grid and LDS: min(blocks, WPC per CU); the LDS
-// request caps residency at WPC workgroups per CU (the grid assumes it)
-int launch_pipe(const pe_handle* h, const StepArgs& a, hipStream_t s) {
-  const int wpc = h->pipe_wpc;
-  const int64_t nblk = ((int64_t)h->n + kQuadEnvs - 1) / kQuadEnvs;
-  dim3 grid((unsigned)std::min<int64_t>(nblk, (int64_t)wpc * h->num_cus)), block(256);
-  size_t lds = quad_lds_bytes(h->g, false, false);
-  if (wpc < 4) lds = std::max(lds, (size_t)160 * 1024 / (wpc + 1) + 16);
-  switch (wpc) {
-    case 2: hipLaunchKernelGGL((pe_step_pipe<16, 6, 2>), grid, block, lds, s, a); break;
-    case 3: hipLaunchKernelGGL((pe_step_pipe<16, 6, 3>), grid, block, lds, s, a); break;
-    default: hipLaunchKernelGGL((pe_step_pipe<16, 6, 4>), grid, block, lds, s, a); break;
-  }
-  PE_HIP(hipGetLastError());
-  return PE_OK;
-}
-#endif
-
 int launch_step(const pe_handle* h, const StepArgs& a, hipStream_t s) {
-#ifdef PE_DEBUG_KNOBS
-  if (h->pipe_wpc > 0) return launch_pipe(h, a, s);
-#endif
   if (is_far(h->variant)) {
     dim3 grid((unsigned)((h->n + kQuadEnvs - 1) / kQuadEnvs)), block(64 * kFarWaves);
     size_t lds = step_lds_bytes(h->g, h->variant, true);
@@ -3310,65 +2996,40 @@ int launch_step(const pe_handle* h, const StepArgs& a, hipStream_t s) {
     dim3 grid((unsigned)((h->n + epb - 1) / epb)), block(nw * 64);
     size_t lds = step_lds_bytes(h->g, h->variant, h->tile_codes);
     if (h->lds_floor > lds) lds = h->lds_floor;  // diagnostics: caps workgroups per CU
-#ifdef PE_DEBUG_KNOBS  // 8 waves of 64 envs: the PE_QUAD_WAVES=8 A/B only (they spill: never in the product)
-#define PE_QUAD(CC, RR, OW)                                                                 \
-  if (h->tile_codes)                                                                        \
-    hipLaunchKernelGGL((pe_step_quad<CC, RR, OW, 4, true>), grid, block, lds, s, a);        \
-  else if (nw == 8)                                                                         \
-    hipLaunchKernelGGL((pe_step_quad<CC, RR, OW, 8>), grid, block, lds, s, a);              \
-  else                                                                                      \
-    hipLaunchKernelGGL((pe_step_quad<CC, RR, OW, 4>), grid, block, lds, s, a);
-#else
-#define PE_QUAD(CC, RR, OW)                                                                 \
-  if (h->tile_codes)                                                                        \
-    hipLaunchKernelGGL((pe_step_quad<CC, RR, OW, 4, true>), grid, block, lds, s, a);        \
-  else                                                                                      \
-    hipLaunchKernelGGL((pe_step_quad<CC, RR, OW, 4>), grid, block, lds, s, a);
-#endif
-#define PE_QUAD4(CC, RR, OW) hipLaunchKernelGGL((pe_step_quad<CC, RR, OW, 4>), grid, block, lds, s, a);
+#define PE_QUAD(...) hipLaunchKernelGGL((pe_step_quad<__VA_ARGS__>), grid, block, lds, s, a)
     switch (h->variant) {
       case V_QUAD_C16R6_1W:
         if (epb == 16 && !h->tile_codes && nw == 8)
-          hipLaunchKernelGGL((pe_step_quad<16, 6, true, 8, false, 16>), grid, block, lds, s, a);
+          PE_QUAD(16, 6, true, 8, false, 16);
         else if (epb == 16 && !h->tile_codes)
-          hipLaunchKernelGGL((pe_step_quad<16, 6, true, 4, false, 16>), grid, block, lds, s, a);
+          PE_QUAD(16, 6, true, 4, false, 16);
         else if (epb == 32 && !h->tile_codes)
-          hipLaunchKernelGGL((pe_step_quad<16, 6, true, 4, false, 32>), grid, block, lds, s, a);
+          PE_QUAD(16, 6, true, 4, false, 32);
+        else if (h->tile_codes)
+          PE_QUAD(16, 6, true, 4, true);
         else
-          PE_QUAD(16, 6, true);
+          PE_QUAD(16, 6, true, 4);
         break;
-      case V_QUAD_C16R6:
-#if PE_GR2
-        if (h->gr2)
-          hipLaunchKernelGGL((pe_step_quad<16, 6, false, 4, false, kQuadEnvs, true>), grid, block, lds, s, a);
-        else
-#endif
-          PE_QUAD4(16, 6, false);
-        break;
-#ifdef PE_DEBUG_KNOBS
-      case V_QUAD_C64R6: PE_QUAD(64, 6, false); break;  // (PE_TILE_CODES=0: the f32-tile A/B)
-#else
-      case V_QUAD_C64R6: hipLaunchKernelGGL((pe_step_quad<64, 6, false, 4, true>), grid, block, lds, s, a); break;
-#endif
-      case V_QUAD_C10R2_1W: PE_QUAD4(10, 2, true); break;
-      case V_QUAD_C10R2: PE_QUAD4(10, 2, false); break;
-      case V_QUAD_C16R4_1W: PE_QUAD4(16, 4, true); break;
+      case V_QUAD_C16R6: PE_QUAD(16, 6, false, 4); break;
+      case V_QUAD_C64R6: PE_QUAD(64, 6, false, 4, true); break;
+      case V_QUAD_C10R2_1W: PE_QUAD(10, 2, true, 4); break;
+      case V_QUAD_C10R2: PE_QUAD(10, 2, false, 4); break;
+      case V_QUAD_C16R4_1W: PE_QUAD(16, 4, true, 4); break;
       case V_QUAD_RT_1W:
         if (h->tile_codes)
-          hipLaunchKernelGGL((pe_step_quad<0, 0, true, 4, true>), grid, block, lds, s, a);
+          PE_QUAD(0, 0, true, 4, true);
         else
-          PE_QUAD4(0, 0, true);
+          PE_QUAD(0, 0, true, 4);
         break;
       case V_QUAD_RT:
         if (h->tile_codes)
-          hipLaunchKernelGGL((pe_step_quad<0, 0, false, 4, true>), grid, block, lds, s, a);
+          PE_QUAD(0, 0, false, 4, true);
         else
-          PE_QUAD4(0, 0, false);
+          PE_QUAD(0, 0, false, 4);
         break;
-      default: PE_QUAD4(16, 4, false); break;
+      default: PE_QUAD(16, 4, false, 4); break;
     }
 #undef PE_QUAD
-#undef PE_QUAD4
   } else {
     dim3 grid((unsigned)((h->n + kBlock - 1) / kBlock)), block(kBlock);
     size_t lds = lds_bytes(h->g);
@@ -3650,12 +3311,11 @@ int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** ou
   // A/B knobs of the measurement tools (tools/ab_build.sh builds a SEPARATE library
   // with -DPE_DEBUG_KNOBS); the product library reads no environment variable.
   bool lane_kernels = false;
-  h->quad_waves = 4;  // measured best at C=16 and C=64 (profiles/r1c-r1e)
+  h->quad_waves = 4;  // measured best at C=16 and C=64 (profiles/r1c-r1e); 8: the 16-env shape below
   h->stagger = 0;
   h->lds_floor = 0;
 #ifdef PE_DEBUG_KNOBS
   if (const char* kenv = std::getenv("PE_STEP_KERNEL")) lane_kernels = std::strcmp(kenv, "lane") == 0;
-  if (const char* qw = std::getenv("PE_QUAD_WAVES")) h->quad_waves = std::atoi(qw) == 8 ? 8 : 4;
   if (const char* sg = std::getenv("PE_STAGGER")) h->stagger = std::atoi(sg);
   if (const char* lf = std::getenv("PE_LDS_FLOOR")) h->lds_floor = std::min<size_t>(std::strtoul(lf, nullptr, 10), 160 * 1024);
 #endif
@@ -3677,9 +3337,7 @@ int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** ou
   // (33 <= C <= 64: with the byte-coded tile, below)
   if (!lane_kernels && h->variant == V_GENERIC && C >= 4 && C <= kRtCMaxBT && R >= 2 && R <= kRtRMax)
     h->variant = oneword ? V_QUAD_RT_1W : V_QUAD_RT;
-  // the sector kernels of these geometries (and the runtime-(C, R) one) exist with 4 waves only
-  if (h->variant >= V_QUAD_C10R2_1W) h->quad_waves = 4;
-  if (h->variant == V_QUAD_C16R6_1W && g.NW != 4) h->variant = V_C16R6_1W;  // needs 16-B visit rows
+  // (V_QUAD_C16R6_1W has 16-B visit rows: WPR == 1 at R = 6 means 2 (G + 12) <= 64, so G <= 20 and NW == 4)
   // byte-coded obs tile where the f32 tile limits the sector kernel's occupancy
   // (C = 64: 89 KB -> 22 KB of LDS per workgroup)
   h->tile_codes = h->variant == V_QUAD_C64R6 || is_far(h->variant) ||
@@ -3697,7 +3355,7 @@ int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** ou
   }
 #ifdef PE_DEBUG_KNOBS
   if (const char* tc = std::getenv("PE_TILE_CODES"))
-    if (h->variant == V_QUAD_C16R6_1W || h->variant == V_QUAD_C64R6) h->tile_codes = std::atoi(tc) != 0;
+    if (h->variant == V_QUAD_C16R6_1W) h->tile_codes = std::atoi(tc) != 0;
 #endif
   // obs as byte codes at the boundary (pe_step_codes): the byte-coded tile kernels
   h->obs_codes = c->obs_codes ? 1 : 0;
@@ -3713,7 +3371,6 @@ int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** ou
     h->tile_codes = 1;
   }
   if (h->tile_codes) {
-    h->quad_waves = 4;
     // (not the byte-coded C16 kernel -- config 5's codes step: its quarters started apart
     // cost it ~0.9 us desynchronized, 11.68 -> 10.75 us without, profiles/r6c/ab_codesstag;
     // the runtime byte-tile kernel keeps it: 32x32/C24/R9 17.0 -> 18.1 us without)
@@ -3746,7 +3403,7 @@ int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** ou
   // (up to 4096 envs: 8 waves x 16 envs -- two waves per SIMD on every CU, sectors of 2
   // rays: 2048 envs 4.56 -> 4.41 us, 4096 4.56 -> 4.49; 8192 4.82 -> 4.98 us, kept at 4)
   h->quad_epb = kQuadEnvs;
-  if (h->variant == V_QUAD_C16R6_1W && !h->tile_codes && h->quad_waves == 4) {
+  if (h->variant == V_QUAD_C16R6_1W && !h->tile_codes) {
     h->quad_epb = n_envs <= kSmallBatch16 ? 16 : (n_envs <= kSmallBatch32 ? 32 : kQuadEnvs);
     if (n_envs <= kSmallBatch8W) h->quad_waves = 8;
   }
@@ -3754,25 +3411,12 @@ int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** ou
   if (const char* ep = std::getenv("PE_QUAD_EPB"))
     if (h->variant == V_QUAD_C16R6_1W && !h->tile_codes) {
       const int v = std::atoi(ep);
-      h->quad_epb = v == 16 || (v == 32 && h->quad_waves == 4) ? v : kQuadEnvs;  // 8 waves: 16 or 64
+      h->quad_epb = v == 16 || v == 32 ? v : kQuadEnvs;
+      if (h->quad_epb != 16) h->quad_waves = 4;  // (the 8-wave kernel exists with 16 envs only)
     }
 #endif
   h->num_cus = prop.multiProcessorCount;
-  h->pipe_wpc = 0;
-#ifdef PE_DEBUG_KNOBS
-  // the persistent pipelined kernel (pe_pipe.hpp, A/B): the headline geometry's 64-env,
-  // 4-wave, f32-tile kernel at batches that fill the chip
-  if (const char* pp = std::getenv("PE_PIPE"))
-    h->pipe_wpc = n_envs > kSmallBatch32 ? std::min(std::max(std::atoi(pp), 0), 4) : 0;
-#endif
-  if (h->pipe_wpc == 1) h->pipe_wpc = 2;
-  if (!(h->variant == V_QUAD_C16R6_1W && h->quad_epb == kQuadEnvs && h->quad_waves == 4 && !h->tile_codes))
-    h->pipe_wpc = 0;
   h->kname = variant_name(h->variant);
-  if (h->pipe_wpc > 0) {
-    std::snprintf(h->kname_buf, sizeof(h->kname_buf), "pe_step_pipe<C16,R6,1word,P%d>", h->pipe_wpc);
-    h->kname = h->kname_buf;
-  }
   if (h->quad_epb != kQuadEnvs) {
     std::snprintf(h->kname_buf, sizeof(h->kname_buf), "%.*s%s,E%d>", (int)std::strlen(h->kname) - 1, h->kname,
                   h->quad_waves == 8 ? ",W8" : "", h->quad_epb);
@@ -3781,10 +3425,6 @@ int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** ou
     std::snprintf(h->kname_buf, sizeof(h->kname_buf), "%.*s,bytetile>", (int)std::strlen(h->kname) - 1, h->kname);
     h->kname = h->kname_buf;
   }
-  // the two-word kernel with the loader env's whole grid block in round 1 (pe_step_quad GR2)
-  h->gr2 = PE_GR2 && h->variant == V_QUAD_C16R6 && g.WPR == 2 && G <= kGr2MaxG && !h->tile_codes &&
-           h->quad_waves == 4 && h->quad_epb == kQuadEnvs;
-  if (h->gr2) h->kname = "pe_step_quad<C16,R6,gridr1>";
   // explicit reset-path tuning (pe_config.coop_max_done; -1: the choice above) --
   // applied before the prefetch decision, which depends on it
   if (c->coop_max_done >= 0 && coop_reset_ok(G, R, g.WPR, g.NW, P, C, c->map_generation_algo))

@@ -179,7 +179,7 @@ def test_kernel_selection(name):
 
 
 # the headline geometry above 32768 envs: the 64-env sector kernel (the persistent
-# pipelined one, pe_pipe.hpp, measured slower: a debug-build A/B only)
+# pipelined one measured slower and was removed)
 BIG_KERNEL = "pe_step_quad<C16,R6,1word>"
 
 

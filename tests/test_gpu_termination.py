@@ -24,19 +24,18 @@ pe_far.hpp; the tests cannot observe which path a block took, this is read from 
                    single-done path takes them only if the done env IS e_early (early_hit); the
                    cooperative path (2 <= ndone <= coop_max_done) hands the k-th done env to wave
                    k % 4 and a wave uses its early record only for el == e_early.
-  kEarly2, kRegStage   compiled out in the shipped build (PE_EARLY2 = 0, PE_REG_STAGE = 0): the
-                   multi-word f32 kernels (g25, g21, g32) and the 16-env workgroups of g20 at
-                   n = 279 make no prediction; every done env's record is loaded in the done path.
-                   The scenarios still run there: they pin the unstaged paths, and a later change
-                   that switches either on meets them.
+  no prediction    the multi-word f32 kernels (g25, g21, g32) and the 16-env workgroups of g20 at
+                   n = 279 make none (the round-6 A/B paths that did -- two early records, the
+                   register-staged record -- were removed): every done env's record is loaded in
+                   the done path.  The scenarios still run there: they pin the unstaged paths, and
+                   a later change that adds a prediction meets them.
   pe_step_wave     (g24c100, g8r20) one wave per env, no speculation: `reset_now = done && autoreset`.
 
   S1  T at 5                 npred 0, ndone 1: nothing staged; the single-done path loads T's record.
   S2  P at 9, T at 3         npred 1 -> P's record staged / early; ndone 2 -> staged = false, the
                              cooperative path: T (the LOWER index) is the 0th done env, P the 1st.
   S3  P at 3, T at 9         the same with T above P.
-  S4  P at 2 and 11, T at 6  npred 2: nothing staged (kEarly2 is off; were it on, wave 1 would hold
-                             env 11's record but be handed T); ndone 3.
+  S4  P at 2 and 11, T at 6  npred 2: nothing staged (only a single prediction is); ndone 3.
   S5  7 is both P and T      npred 1, ndone 1, the done env is the predicted one: the staged /
                              early record IS used, by an env with terminated and truncated both
                              set, whose return includes r_complete.

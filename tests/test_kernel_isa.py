@@ -3,9 +3,9 @@ are extracted from libplantos_hip.so and
 
 - no function loads through a null scalar base (the kernarg-segment pointer read in
   a noinline callee is 0 on gfx950 / ROCm 7.2: the fault round 4 hit in the
-  pipelined kernel; tools/diag/isa_nullbase.py);
-- no step kernel spills more than 8 VGPRs (the product instantiates none of the
-  spilling A/B shapes, e.g. 8 waves x 64 envs).
+  pipelined kernel, since removed; tools/diag/isa_nullbase.py);
+- no step kernel spills more than 8 VGPRs (the spilling shapes measured in the A/Bs,
+  e.g. 8 waves x 64 envs, are gone from the source).
 """
 import os
 import shutil

@@ -10,7 +10,6 @@ SRC=$ROOT/build/ab/src_$NAME
 rm -rf "$SRC" && mkdir -p "$SRC"
 if [ "$REV" = WORKTREE ]; then
   mkdir -p "$SRC/rl-env_amd" "$SRC/tools/diag" && cp -r "$ROOT/rl-env_amd/csrc" "$SRC/rl-env_amd/" && cp -r "$ROOT/include" "$SRC/"
-  cp "$ROOT/tools/diag/pe_pipe.hpp" "$SRC/tools/diag/"  # (the debug-only pipelined kernel)
 else
   git -C "$ROOT" archive "$REV" rl-env_amd/csrc include | tar -x -C "$SRC"
   git -C "$ROOT" archive "$REV" tools/diag 2>/dev/null | tar -x -C "$SRC" || true

@@ -75,7 +75,7 @@ def run(argv):
     # envs per workgroup and waves per workgroup of the stamped kernel (the small-batch shapes:
     # E16 with 8 waves at <= 4096 envs, E16 / E32 with 4 waves up to 32768; --epb / --waves)
     EPB = arg("--epb", 64)
-    NWQ = arg("--waves", int(os.environ.get("PE_QUAD_WAVES", "4")))
+    NWQ = arg("--waves", 4)
     nw = (n + EPB - 1) // EPB * NWQ
     buf = np.zeros(nw * 8, np.uint64)
     _capi.check(L.pe_debug_stamps(buf.ctypes.data_as(ctypes.c_void_p), buf.size), "stamps")
