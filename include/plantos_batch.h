@@ -370,6 +370,14 @@ int pe_policy_load(pe_policy* p, const pe_policy_tower* towers, void* stream);
  * sync, no allocation: graph-capturable. */
 int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32_t mode, uint64_t seed,
                       uint32_t t, int32_t* actions, float* head0_or_null, float* head1_or_null, void* stream);
+/* pe_policy_forward in PE_POLICY_ARGMAX mode over `rows` >= 1 rows of obs instead of the
+ * handle's n envs (a sampled minibatch; rows may be smaller or larger than n): obs u8[rows, D]
+ * or f32[rows, D], actions i32[rows], head0 f32[rows, A] / head1 f32[rows] or NULL.  The
+ * same kernel with another row count: row r has the bits pe_policy_forward_host gives for
+ * that row.  Nothing past row rows - 1 is read or written.  PE_ERR_ARG for rows < 1, a
+ * recurrent policy, and what pe_policy_forward refuses. */
+int pe_policy_forward_rows(pe_policy* p, int32_t rows, const void* obs, int32_t obs_is_codes, int32_t* actions,
+                           float* head0_or_null, float* head1_or_null, void* stream);
 /* The host twin: the definition above in plain C++ on HOST arrays (no handle, no device).
  * obs f32[n, D]; towers with host tensors; outputs as pe_policy_forward (head0 / head1
  * may be NULL). */
@@ -540,6 +548,106 @@ int pe_rollout_gae(int32_t T, int32_t n, int64_t reward_stride, int64_t value_st
 int pe_rollout_gae_host(int32_t T, int32_t n, int64_t reward_stride, int64_t value_stride, int64_t start_stride,
                         int64_t out_stride, const float* rewards, const float* values, const uint8_t* starts,
                         const float* last_values, double gamma, double gae_lambda, float* advantages, float* returns);
+
+/* Replay collection: what SB3 2.2.1's OffPolicyAlgorithm.collect_rollouts, DQN.predict /
+ * _sample_action, ReplayBuffer.add / sample and the target half of DQN.train add to the
+ * act / step loop of a DQN (DQN("MlpPolicy", buffer_size=2000000, batch_size=64, gamma=0.99,
+ * exploration_fraction=0.7, exploration_initial_eps=1.0, exploration_final_eps=0.05,
+ * net_arch=[512,512,256]), trainingCode.py:203-247): epsilon-greedy exploration, the
+ * transition ring with the terminal-observation and time-limit rules, uniform minibatch
+ * sampling and the TD target.  The learner (loss, gradients, optimizer, polyak / hard update
+ * of the target net) stays out of scope.  The functions work on caller-owned arrays; the
+ * device ones run on the calling thread's current device, asynchronous on `stream`, with no
+ * allocation and no sync (graph-capturable); the *_host twins execute the same definition on
+ * host arrays and give the same bits (rl-env_amd/csrc/pe_replay_math.hpp).  Obs are byte
+ * codes throughout (handles created with obs_codes; D = 5C + 27 bytes per obs): an f32 ring
+ * is not provided.
+ *
+ * Control block: ctrl is a caller-owned DEVICE array of PE_REPLAY_CTRL_WORDS u64 words,
+ * zeroed by the caller before the first call.  Word PE_RC_STEPS counts the rows of
+ * transitions stored so far, word PE_RC_DRAWS the minibatches sampled so far; the rest is
+ * reserved.  The counters live on the device so that a captured graph that is replayed
+ * writes the next ring slot and draws fresh random numbers.  pe_replay_store and
+ * pe_replay_sample advance their counter in a one-thread launch of its own behind the kernel
+ * that reads it: no launch both reads a counter in many workgroups and advances it.
+ * pe_replay_select only reads PE_RC_STEPS.
+ *
+ * Definition:
+ *  - Random words of an event counter c (steps or draws), an index i and a domain word w:
+ *    philox4x32-10(ctr = ((uint32)c, i, (uint32)(c >> 32), w), key = seed) -- (c, i, 0, w)
+ *    for the first 2^32 events.  mulhi32(x, m) = (uint64)x * m >> 32.
+ *  - select, per env e: (x, y, ..) = words(steps, env_id_offset + e, 0x53504545);
+ *    u = (x >> 8) * 2^-24; the env explores iff u < eps, and then takes mulhi32(y, A) --
+ *    uniform over all A actions, the greedy one included, as action_space.sample() --, else
+ *    its greedy action.  eps = 0 reproduces the greedy actions, eps = 1 explores every env
+ *    (SB3's learning_starts phase).  Exploration per env is this project's own definition:
+ *    SB3's DQN.predict draws ONE np.random.rand() for the whole vector of envs, so that all
+ *    envs explore or none does -- an artefact of small n_envs that is useless at 65536 envs --
+ *    and numpy's generator is not reproduced.
+ *  - store, one row of n transitions into ring slot steps % K, per env e: obs and action as
+ *    given; reward as given; done = terminated (SB3's dones * (1 - timeouts), timeout =
+ *    truncated && !terminated: an episode cut by the time limit alone still bootstraps);
+ *    next_obs = the step's next obs where !(terminated | truncated), else the byte codes of
+ *    the env's terminal obs (SB3's _store_transition: infos[i]["terminal_observation"]),
+ *    encoded from the step's f32 terminal_obs row: column c < 5C: c % 5 == 0 -> rint(x R),
+ *    else x != 0 ? R + 1 : 0; the two position columns 96 + rint(x G); the 25 visit columns
+ *    80 + rint(10 x); products in f64, round-half-even (plantos_amd/codes.py encode_obs;
+ *    expanding the code gives x back bit for bit).  Rows of terminal_obs of envs that are
+ *    not done are never read.  A done env adds 1 to ep_count, episode_return to
+ *    ep_return_sum and episode_length to ep_length_sum (per env, no atomics).  Then steps
+ *    advances by 1.
+ *  - sample, draw number `draws`, per sample j < B: filled = min(steps, K);
+ *    (x, y, ..) = words(draws, j, 0x504D4153); slot = mulhi32(x, filled); env = mulhi32(y, n):
+ *    uniform with replacement over what is stored, as ReplayBuffer.sample.  The outputs are
+ *    the ring's rows at (slot, env) and the index pair.  With filled == 0 the indices are
+ *    (-1, -1) and every other output row is zero.  Then draws advances by 1.
+ *  - target, per sample j: g = (float)gamma; m = q_next[j][a*], a* the first maximum in action
+ *    order; target = reward + (g * m) * (1 - (float)(done != 0)), every product and sum
+ *    rounded on its own.
+ *
+ * Ring planes (caller-owned, device): obs / next_obs u8[K, n, D], actions i32[K, n], rewards
+ * f32[K, n], dones u8[K, n].  PE_ERR_ARG with a message for sizes < 1, A outside 2..8, a NULL
+ * required pointer, a geometry with D = 5C + 27 > 4096, and an output of pe_replay_sample or
+ * a ring plane that is not 4-byte aligned. */
+#define PE_REPLAY_CTRL_WORDS 4
+enum pe_replay_ctrl { PE_RC_STEPS = 0, PE_RC_DRAWS = 1 };
+
+/* greedy i32[n] (a forward's argmax actions), eps f32[1] (DEVICE: a schedule advances without
+ * recapture), actions i32[n] (may be `greedy`), explored u8[n] or NULL (1 where the env
+ * explored). */
+int pe_replay_select(int32_t n, int32_t A, const int32_t* greedy, const float* eps, const uint64_t* ctrl,
+                     uint64_t seed, uint32_t env_id_offset, int32_t* actions, uint8_t* explored_or_null,
+                     void* stream);
+int pe_replay_select_host(int32_t n, int32_t A, const int32_t* greedy, float eps, uint64_t steps, uint64_t seed,
+                          uint32_t env_id_offset, int32_t* actions, uint8_t* explored_or_null);
+/* obs u8[n, D] (the codes the policy acted on), actions i32[n], next_obs u8[n, D], reward
+ * f32[n], terminated / truncated u8[n], terminal_obs f32[n, D] as pe_step_codes left them;
+ * episode_return f64[n] / episode_length i32[n] or NULL; the accumulators may each be NULL.
+ * There is no host twin: the definition is a copy plus the encoder (plantos_amd/replay.py
+ * HostRing states it in numpy). */
+int pe_replay_store(int32_t n, int32_t K, int32_t grid_size, int32_t lidar_range, int32_t lidar_channels,
+                    const uint8_t* obs, const int32_t* actions, const uint8_t* next_obs, const float* reward,
+                    const uint8_t* terminated, const uint8_t* truncated, const float* terminal_obs,
+                    const double* episode_return_or_null, const int32_t* episode_length_or_null,
+                    uint8_t* ring_obs, uint8_t* ring_next_obs, int32_t* ring_actions, float* ring_rewards,
+                    uint8_t* ring_dones, int32_t* ep_count_or_null, double* ep_return_sum_or_null,
+                    int32_t* ep_length_sum_or_null, uint64_t* ctrl, void* stream);
+/* Outputs, dense: obs / next_obs u8[B, D], actions i32[B], rewards f32[B], dones u8[B],
+ * indices i32[B, 2] = (slot, env).  Nothing past those extents is written. */
+int pe_replay_sample(int32_t B, int32_t n, int32_t K, int32_t D, const uint8_t* ring_obs,
+                     const uint8_t* ring_next_obs, const int32_t* ring_actions, const float* ring_rewards,
+                     const uint8_t* ring_dones, uint64_t seed, uint64_t* ctrl, uint8_t* obs, uint8_t* next_obs,
+                     int32_t* actions, float* rewards, uint8_t* dones, int32_t* indices, void* stream);
+/* The indices pe_replay_sample draws with the counters at (steps, draws); the gather itself
+ * is a copy. */
+int pe_replay_sample_indices_host(int32_t B, int32_t n, int32_t K, uint64_t steps, uint64_t draws, uint64_t seed,
+                                  int32_t* indices);
+/* q_next f32[B, A] (the target network's Q-values of next_obs), rewards f32[B], dones u8[B];
+ * targets f32[B]. */
+int pe_replay_target(int32_t B, int32_t A, const float* q_next, const float* rewards, const uint8_t* dones,
+                     double gamma, float* targets, void* stream);
+int pe_replay_target_host(int32_t B, int32_t A, const float* q_next, const float* rewards, const uint8_t* dones,
+                          double gamma, float* targets);
 
 /* Introspection for tests / benchmarks. */
 int32_t pe_num_envs(const pe_handle* h);

@@ -1,6 +1,6 @@
 // pe_policy.hip -- batched MLP policy inference from the obs of a handle's envs to their
-// next actions: pe_policy_create / _load / _forward / _value / _destroy of include/plantos_batch.h
-// (the definition of the outputs heads that header's "Policy inference" block; the host
+// next actions: pe_policy_create / _load / _forward / _forward_rows / _value / _destroy of
+// include/plantos_batch.h (the definition of the outputs heads that header's "Policy inference" block; the host
 // twin is pe_policy_host.cpp and shares pe_policy_math.hpp with this file; the pieces the
 // recurrent policy of pe_policy_lstm.hip uses too are in pe_policy_impl.hpp).
 //
@@ -257,6 +257,31 @@ int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32
     hipLaunchKernelGGL(pe_policy_forward_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
   const hipError_t le = hipGetLastError();
   return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_forward");
+}
+
+int pe_policy_forward_rows(pe_policy* p, int32_t rows, const void* obs, int32_t obs_is_codes, int32_t* actions,
+                           float* head0, float* head1, void* stream) {
+  if (!p || !obs || !actions) return fail(PE_ERR_ARG, "null argument");
+  if (p->H) return fail(PE_ERR_ARG, "pe_policy_forward_rows does not evaluate a recurrent policy");
+  if (rows < 1) return fail(PE_ERR_ARG, "rows must be >= 1, got " + std::to_string(rows));
+  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
+  if (head1 && p->n_towers < 2) return fail(PE_ERR_ARG, "head1 needs a second tower");
+  FwdArgs a = fwd_args(p, obs, obs_is_codes);
+  a.n = rows;  // the kernel bounds its last tile, its loads and its stores by a.n
+  a.mode = PE_POLICY_ARGMAX;
+  a.actions = actions;
+  a.head0 = head0;
+  a.head1 = head1;
+  DevBind db(p->h->device);
+  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  const int E = p->env_tile;
+  const dim3 grid((unsigned)(((int64_t)a.n + E - 1) / E)), block(kThreads);
+  if (E == 64)
+    hipLaunchKernelGGL(pe_policy_forward_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
+  else
+    hipLaunchKernelGGL(pe_policy_forward_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
+  const hipError_t le = hipGetLastError();
+  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_forward_rows");
 }
 
 int pe_policy_value(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* want, const uint8_t* unless,

@@ -22,6 +22,8 @@
 namespace pe_pol {
 
 constexpr uint32_t kDomainPolicy = 0x594C4F50u;  // Philox counter domain word of the action sampler
+constexpr uint32_t kDomainEps = 0x53504545u;     // ... of epsilon-greedy exploration (pe_replay_select)
+constexpr uint32_t kDomainSample = 0x504D4153u;  // ... of minibatch sampling (pe_replay_sample)
 
 PE_HD float bits_to_float(uint32_t u) {
   float f;

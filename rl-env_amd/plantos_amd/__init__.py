@@ -10,11 +10,14 @@ Public surface:
                     bootstrap and GAE (SB3's collect_rollouts); returns a Rollout
   RecurrentRolloutCollector  the same under a RecurrentPolicy (sb3_contrib's RecurrentPPO), with
                     snapshots of the LSTM state in the Rollout
+  ReplayCollector   DQN's collection on the device: epsilon-greedy exploration, the transition
+                    ring, uniform minibatch sampling (a ReplayBatch) and TD targets
 """
 from .batch import PlantOSBatch  # noqa: F401
 from .policy import Policy, RecurrentPolicy  # noqa: F401
+from .replay import ReplayBatch, ReplayCollector, linear_eps  # noqa: F401
 from .rollout import RecurrentRolloutCollector, Rollout, RolloutCollector  # noqa: F401
 from .vec_env import PlantOSVecEnv, PlantOSVectorEnv  # noqa: F401
 
 __all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy", "Rollout",
-           "RolloutCollector", "RecurrentRolloutCollector"]
+           "RolloutCollector", "RecurrentRolloutCollector", "ReplayBatch", "ReplayCollector", "linear_eps"]

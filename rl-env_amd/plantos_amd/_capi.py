@@ -49,7 +49,12 @@ EXPORTS = [
     "pe_policy_value", "pe_policy_value_lstm",
     "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
     "pe_logf_host",
+    "pe_policy_forward_rows",
+    "pe_replay_select", "pe_replay_select_host", "pe_replay_store", "pe_replay_sample",
+    "pe_replay_sample_indices_host", "pe_replay_target", "pe_replay_target_host",
 ]
+PE_REPLAY_CTRL_WORDS = 4
+PE_RC_STEPS, PE_RC_DRAWS = 0, 1
 PE_ACT_TANH, PE_ACT_RELU = 0, 1
 PE_POLICY_ARGMAX, PE_POLICY_SAMPLE = 0, 1
 
@@ -181,7 +186,19 @@ def lib():
         L.pe_rollout_gae.argtypes = gae + [P]
         L.pe_rollout_gae_host.argtypes = gae
         L.pe_logf_host.argtypes = [I32, P, P]
-    for name in ("pe_policy_value", "pe_policy_value_lstm", "pe_logf_host", "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
+    if hasattr(L, "pe_replay_select"):  # (an older library loaded for a same-box A/B lacks them)
+        F = ctypes.c_float
+        L.pe_policy_forward_rows.argtypes = [P, I32, P, I32, P, P, P, P]
+        L.pe_replay_select.argtypes = [I32, I32, P, P, P, U64, U32, P, P, P]
+        L.pe_replay_select_host.argtypes = [I32, I32, P, F, U64, U64, U32, P, P]
+        L.pe_replay_store.argtypes = [I32, I32, I32, I32, I32] + [P] * 19
+        L.pe_replay_sample.argtypes = [I32, I32, I32, I32, P, P, P, P, P, U64, P, P, P, P, P, P, P, P]
+        L.pe_replay_sample_indices_host.argtypes = [I32, I32, I32, U64, U64, U64, P]
+        L.pe_replay_target.argtypes = [I32, I32, P, P, P, D, P, P]
+        L.pe_replay_target_host.argtypes = [I32, I32, P, P, P, D, P]
+    for name in ("pe_policy_forward_rows", "pe_replay_select", "pe_replay_select_host", "pe_replay_store",
+                 "pe_replay_sample", "pe_replay_sample_indices_host", "pe_replay_target", "pe_replay_target_host",
+                 "pe_policy_value", "pe_policy_value_lstm", "pe_logf_host", "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
                  "pe_policy_create_lstm", "pe_policy_load_lstm", "pe_policy_forward_lstm",
                  "pe_policy_lstm_reset_state", "pe_policy_lstm_get_state", "pe_policy_lstm_set_state",
                  "pe_policy_lstm_forward_host", "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward",

@@ -354,6 +354,48 @@ class Policy:
             C.check(rc, "pe_policy_forward")
         return a, lg, v
 
+    def act_rows(self, obs, out=None):
+        """(actions i32 [rows], logits f32 [rows, A], values f32 [rows] or None) of any number of
+        obs rows: the argmax forward over a contiguous device tensor [rows, D], rows >= 1,
+        uint8 codes (obs_codes batches) or float32 -- a sampled minibatch rather than the
+        batch's n envs (pe_policy_forward_rows: the same kernel, the same bits per row as
+        `host_forward`).  out: (actions, logits, values) tensors of those shapes to write
+        (logits / values may be None: not asked for); without it new tensors are allocated.
+        One kernel on the current stream; no sync, and with `out` no allocation:
+        graph-capturable."""
+        torch = self._torch
+        b = self.batch
+        D, A = b.obs_dim, self.towers[0][-1]
+        if not (type(obs) is torch.Tensor and obs.is_cuda and obs.get_device() == b._dev_index
+                and obs.is_contiguous() and obs.dim() == 2 and obs.shape[0] >= 1 and obs.shape[1] == D
+                and (obs.dtype is torch.float32 or obs.dtype is torch.uint8)):
+            raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape (rows >= 1, {D}) on {b.device}")
+        rows = int(obs.shape[0])
+        codes = obs.dtype is torch.uint8
+        if codes and not b.obs_codes:
+            raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
+        if out is None:
+            out = (torch.empty(rows, dtype=torch.int32, device=b.device),
+                   torch.empty((rows, A), dtype=torch.float32, device=b.device),
+                   torch.empty(rows, dtype=torch.float32, device=b.device) if len(self.towers) == 2 else None)
+        a, lg, v = out
+        for name, x, dt, shape in (("actions", a, torch.int32, (rows,)), ("logits", lg, torch.float32, (rows, A)),
+                                   ("values", v, torch.float32, (rows,))):
+            if x is None and name != "actions":
+                continue  # an output not asked for
+            if not (type(x) is torch.Tensor and x.dtype is dt and x.is_cuda and x.get_device() == b._dev_index
+                    and x.is_contiguous() and tuple(x.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {b.device}")
+        if v is not None and len(self.towers) < 2:
+            raise ValueError("a one-tower policy has no values")
+        rc = C.lib().pe_policy_forward_rows(self._handle(), rows, obs.data_ptr(), int(codes), a.data_ptr(),
+                                            lg.data_ptr() if lg is not None else None,
+                                            v.data_ptr() if v is not None else None,
+                                            torch.cuda.current_stream(b._dev_index).cuda_stream)
+        if rc:
+            C.check(rc, "pe_policy_forward_rows")
+        return a, lg, v
+
     def value(self, obs=None, select=None, out=None):
         """The values f32 [n] alone: the value tower's head, bit for bit what `act` returns as
         values for the same obs, without the action tower and the sampler (`t` stays).
