@@ -4,6 +4,25 @@
 #include "../../include/plantos_batch.h"
 #include "pe_device.hpp"
 
+namespace pe {
+// A handle's step kernel, by what it is.  pe_plan.hpp chooses it; the launch, its LDS size, its
+// name, the ray-table format and pe_kernel_variant() all read this one choice.
+enum class StepFamily : int {
+  wave,  // pe_step_wave: one wave per env, any geometry
+  fast,  // pe_step_fast<C, R, ONEWORD>: one lane per env (A/B measurement, debug builds only)
+  quad,  // pe_step_quad<C, R, ONEWORD, NW, BT, EPB>: the sector kernel
+  far    // pe_step_far<C, R>: the sector kernel of long LIDAR ranges
+};
+struct StepKernel {
+  StepFamily family;
+  int C, R;       // the compile-time LIDAR table (lidar_tables.inc); 0, 0: rays from the runtime table
+  bool oneword;   // the whole padded grid row in one u64 and 16-B visit rows
+  bool bytetile;  // the obs tile holds byte codes (pe_step_quad<..., BT>); so do the prefetched records' obs rows
+  int epb;        // envs per workgroup (the sector kernel: 64; 16 / 32 for small batches, C16R6 one-word)
+  int waves;      // waves per workgroup (the sector kernel: 4; 8 with 16-env workgroups up to 4096 envs)
+};
+}  // namespace pe
+
 struct pe_handle {
   int device;
   int n;
@@ -13,17 +32,12 @@ struct pe_handle {
   pe::State st;
   void* mem;
   size_t bytes;
-  int variant;
-  int tile_codes;    // the sector kernel's obs tile holds byte codes (pe_step_quad<..., BT>); so do the
-                     // prefetched records' obs rows
-  int obs_codes;     // pe_config.obs_codes: pe_step_codes allowed (implies tile_codes)
-  const char* kname;
-  char kname_buf[64];  // kname with the envs-per-workgroup suffix (small batches)
+  pe::StepKernel k;
+  int obs_codes;     // pe_config.obs_codes: pe_step_codes allowed (implies k.bytetile)
+  char kname[64];    // the step kernel's name (pe_kernel_name)
   void* cur_mem;     // CurriculumWrapper records (pe_curriculum_enable), or NULL
   size_t lds_floor;  // minimum dynamic LDS per step workgroup (PE_LDS_FLOOR, debug builds only)
-  int quad_waves;    // waves per workgroup of the sector kernel (4; 8 with 16-env workgroups up to 4096 envs)
-  int quad_epb;      // envs per workgroup of the sector kernel (64; 16 / 32 for small batches, C16R6 one-word)
-  int stagger;       // sector-kernel start delay per block quarter (PE_STAGGER, debug builds only)
+  int stagger;       // sector-kernel start delay per block quarter (byte-tile kernels; PE_STAGGER in debug builds)
   int num_cus;       // the device's CUs
   int coop_max_done; // wave-cooperative auto-resets up to this many done envs per block (pe_coop.hpp;
                      // pe_config.coop_max_done)
@@ -40,5 +54,16 @@ extern "C" int pe_internal_set_error(int code, const char* msg);
 // pe_internal_flush_vx (plantos_batch.hip): the steps' deferred visit-overflow writes applied
 // on `stream` (before anything reads the exact visit counts, e.g. the MCTS clone).
 extern "C" int pe_internal_flush_vx(const pe_handle* h, void* stream);
+// pe_internal_plan (plantos_batch.hip): what pe_create would decide for (config, n_envs) on a
+// device of num_cus CUs, before it touches a device (pe_plan.hpp) -- no HIP call.  On rejection
+// pe_create's error code, with pe_last_error() set.
+struct pe_plan_info {
+  int32_t variant;       // pe_kernel_variant()
+  char kernel_name[64];  // pe_kernel_name()
+  int32_t tile_codes, stagger, quad_epb, quad_waves, coop_max_done, prefetch_every;
+  uint64_t state_bytes;     // pe_state_bytes(): the main allocation
+  uint64_t prefetch_bytes;  // the prefetched resets' allocation (0: none)
+};
+extern "C" int pe_internal_plan(const pe_config* c, int32_t n_envs, int32_t num_cus, pe_plan_info* out);
 // pe_internal_render_free (pe_render.hip): frees the handle's render tables (pe_destroy).
 extern "C" void pe_internal_render_free(pe_handle* h);

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -2891,14 +2892,13 @@ int hip_fail(hipError_t e, const char* what) {
     if (_e != hipSuccess) return hip_fail(_e, #call);  \
   } while (0)
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Binds the handle's device for one API call and restores the caller's device
 // afterwards (the library never leaves the calling thread on another device).
 struct DeviceGuard {
   int prev = -1;
   int rc = PE_OK;
-  explicit DeviceGuard(const pe_handle* h) {
+  explicit DeviceGuard(const pe_handle* h) : DeviceGuard(h->device) {}
+  explicit DeviceGuard(int device) {
     // hipGetLastError() reports the last failed runtime call of this thread,
     // whoever made it (torch probes, the caller's own calls): drop such a stale
     // error so the launch checks below see only this call's launches.
@@ -2909,8 +2909,8 @@ struct DeviceGuard {
       prev = -1;
       return;
     }
-    if (prev != h->device) {
-      e = hipSetDevice(h->device);
+    if (prev != device) {
+      e = hipSetDevice(device);
       if (e != hipSuccess) rc = hip_fail(e, "hipSetDevice");
     } else {
       prev = -1;
@@ -2935,127 +2935,56 @@ StepArgs base_args(const pe_handle* h) {
   return a;
 }
 
-size_t lds_bytes(const Geo& g) {
-  return sizeof(float) * (size_t)(kTabFloats + kBlock * g.DS) + align_up(2 * (size_t)g.C * g.R, 16);
-}
+}  // namespace
 
-// Step kernel variants.  The quadrant kernels (4 waves x 64 envs per workgroup)
-// are the default for the specialized geometries (compile-time C, R: the LIDAR
-// offsets of lidar_tables.inc); the one-lane-per-env kernels stay selectable
-// (PE_STEP_KERNEL=lane, debug builds) for A/B measurement at C16R6 / C64R6.
-// batch sizes up to which the headline kernel runs 16- / 32-env workgroups (quad_epb)
-// (same-box A/B, profiles/r3b_ab_epb*.jsonl: 4096 envs 5.06 -> 4.55 us with 16-env
-// workgroups, 8192: 16 ~ 32, 16384: 32 best, 32768: 32 ~ 64)
-constexpr int kSmallBatch16 = 8192, kSmallBatch32 = 32768, kSmallBatch8W = 4096;
+// make_plan(): geometry, kernel selection, allocation layouts and the host tables -- no HIP call
+#include "pe_plan.hpp"
 
-enum Variant {
-  V_GENERIC = 0, V_C16R6_1W = 1, V_C16R6 = 2, V_C64R6 = 3,
-  V_QUAD_C16R6_1W = 4, V_QUAD_C16R6 = 5, V_QUAD_C64R6 = 6,
-  V_QUAD_C10R2_1W = 7, V_QUAD_C10R2 = 8,  // plantos_env.py:25-26 constructor default (G=21: multi-word)
-  V_QUAD_C16R4_1W = 9, V_QUAD_C16R4 = 10,  // test_environment.py:24 (G=15, C=16, R=4)
-  V_QUAD_RT_1W = 11, V_QUAD_RT = 12,       // runtime (C, R): every other geometry with C <= 64, 2 <= R <= 14
-  V_FAR_C64R32 = 13                         // pe_step_far<64, 32>: SURVEY §8(d)'s R = 32 stress variant
-};
-
-// the prefetched records' obs row stride (bytes; pe_device.hpp Prefetch)
-size_t pf_ostride(const Geo& g, bool codes) { return align_up((size_t)(codes ? g.D : 4 * g.D), 16); }
-
-size_t quad_lds_bytes(const Geo& g, bool codes, bool rt) {
-  const size_t off = (size_t)((kTabFloats + (2 * g.R + 3) * kQuadEnvs * 2 + 7 * kQuadEnvs + 3) & ~3) +
-                     (rt ? (size_t)quad_rtab_floats(g.C, g.R) : 0);  // (+ the runtime kernel's probe table)
-  // + the single-done record's LDS-DMA staging region (pe_coop.hpp pf_stage_issue)
-  size_t stage = (size_t)pf_stage_bytes(g.G, g.WPR, (int)pf_ostride(g, codes));
-  // (f32 kernels: slack left from a removed staging path; shrinking it moves occupancy -- a measured change)
-  const int ng = pf_grid_units(g.G, g.WPR), no = (int)pf_ostride(g, codes) / 16;
-  if (!codes && 1 + ng + no <= 64) stage = std::max(stage, (size_t)((1 + 2 * ng + no + 63) / 64) * 1024);
-  // (byte-coded kernels that stage by LDS-DMA: the record, then the info wave's rows)
-  if (codes && (rt || g.C >= kBtStageMinC) && ng <= 128)
-    stage = std::max(stage, (size_t)((1 + 2 * ng + no + 63) / 64) * 1024);
-  if (codes)  // byte tile + code table (quad_ctab_off)
-    return sizeof(float) * (off + (size_t)((kQuadEnvs * g.D + 15) / 16) * 4 + 256) + stage;
-  return sizeof(float) * (off + (size_t)kQuadEnvs * g.D) + stage;
-}
-
-bool is_quad(int v) { return v >= V_QUAD_C16R6_1W; }
-bool is_far(int v) { return v == V_FAR_C64R32; }
-
-// the step kernel's dynamic LDS (sector kernels)
-size_t step_lds_bytes(const Geo& g, int variant, bool codes) {
-  if (is_far(variant)) return sizeof(float) * (size_t)far_lds_floats(g.G, g.WPR, g.C, g.R);
-  return quad_lds_bytes(g, codes, variant >= V_QUAD_RT_1W);
-}
+namespace {
 
 int launch_step(const pe_handle* h, const StepArgs& a, hipStream_t s) {
-  if (is_far(h->variant)) {
-    dim3 grid((unsigned)((h->n + kQuadEnvs - 1) / kQuadEnvs)), block(64 * kFarWaves);
-    size_t lds = step_lds_bytes(h->g, h->variant, true);
-    if (h->lds_floor > lds) lds = h->lds_floor;  // diagnostics: caps workgroups per CU
-    hipLaunchKernelGGL((pe_step_far<64, 32>), grid, block, lds, s, a);
-  } else if (is_quad(h->variant)) {
-    const int nw = h->quad_waves, epb = h->quad_epb;
-    dim3 grid((unsigned)((h->n + epb - 1) / epb)), block(nw * 64);
-    size_t lds = step_lds_bytes(h->g, h->variant, h->tile_codes);
-    if (h->lds_floor > lds) lds = h->lds_floor;  // diagnostics: caps workgroups per CU
-#define PE_QUAD(...) hipLaunchKernelGGL((pe_step_quad<__VA_ARGS__>), grid, block, lds, s, a)
-    switch (h->variant) {
-      case V_QUAD_C16R6_1W:
-        if (epb == 16 && !h->tile_codes && nw == 8)
-          PE_QUAD(16, 6, true, 8, false, 16);
-        else if (epb == 16 && !h->tile_codes)
-          PE_QUAD(16, 6, true, 4, false, 16);
-        else if (epb == 32 && !h->tile_codes)
-          PE_QUAD(16, 6, true, 4, false, 32);
-        else if (h->tile_codes)
-          PE_QUAD(16, 6, true, 4, true);
-        else
-          PE_QUAD(16, 6, true, 4);
-        break;
-      case V_QUAD_C16R6: PE_QUAD(16, 6, false, 4); break;
-      case V_QUAD_C64R6: PE_QUAD(64, 6, false, 4, true); break;
-      case V_QUAD_C10R2_1W: PE_QUAD(10, 2, true, 4); break;
-      case V_QUAD_C10R2: PE_QUAD(10, 2, false, 4); break;
-      case V_QUAD_C16R4_1W: PE_QUAD(16, 4, true, 4); break;
-      case V_QUAD_RT_1W:
-        if (h->tile_codes)
-          PE_QUAD(0, 0, true, 4, true);
-        else
-          PE_QUAD(0, 0, true, 4);
-        break;
-      case V_QUAD_RT:
-        if (h->tile_codes)
-          PE_QUAD(0, 0, false, 4, true);
-        else
-          PE_QUAD(0, 0, false, 4);
-        break;
-      default: PE_QUAD(16, 4, false, 4); break;
-    }
-#undef PE_QUAD
-  } else {
-    dim3 grid((unsigned)((h->n + kBlock - 1) / kBlock)), block(kBlock);
-    size_t lds = lds_bytes(h->g);
-    switch (h->variant) {
-      case V_C16R6_1W: hipLaunchKernelGGL((pe_step_fast<16, 6, true>), grid, block, lds, s, a); break;
-      case V_C16R6: hipLaunchKernelGGL((pe_step_fast<16, 6, false>), grid, block, lds, s, a); break;
-      case V_C64R6: hipLaunchKernelGGL((pe_step_fast<64, 6, false>), grid, block, lds, s, a); break;
-      default: {  // pe_step_wave: one wave per env
-        const Geo& g = h->g;
-        const size_t wlds = sizeof(float) * ((size_t)wave_hdr_floats(g.C, g.R, wave_aln_ok(g.G, g.R, g.WPR)) +
-                                             kWaveEnvs * (size_t)wave_lds_floats(g.G, g.R, g.WPR, g.NW, g.D));
-        dim3 wgrid((unsigned)((h->n + kWaveEnvs - 1) / kWaveEnvs)), wblock(64 * kWaveEnvs);
-        const bool aln = wave_aln_ok(g.G, g.R, g.WPR);
-        if (g.WPR == 1) {
-          if (aln)
-            hipLaunchKernelGGL((pe_step_wave<1, true>), wgrid, wblock, wlds, s, a);
-          else
-            hipLaunchKernelGGL((pe_step_wave<1, false>), wgrid, wblock, wlds, s, a);
-        } else {
-          if (aln)
-            hipLaunchKernelGGL((pe_step_wave<kCoopWPR, true>), wgrid, wblock, wlds, s, a);
-          else
-            hipLaunchKernelGGL((pe_step_wave<kCoopWPR, false>), wgrid, wblock, wlds, s, a);
-        }
-        break;
+  const StepKernel& k = h->k;
+  dim3 grid((unsigned)((h->n + k.epb - 1) / k.epb)), block(64 * k.waves);
+  size_t lds = step_lds_bytes(h->g, k);
+  switch (k.family) {
+    case StepFamily::far:
+      if (h->lds_floor > lds) lds = h->lds_floor;  // diagnostics: caps workgroups per CU
+      hipLaunchKernelGGL((pe_step_far<64, 32>), grid, block, lds, s, a);
+      break;
+    case StepFamily::quad:
+      if (h->lds_floor > lds) lds = h->lds_floor;  // diagnostics: caps workgroups per CU
+      // the row of PE_QUAD_KERNELS that is the handle's kernel
+#define PE_ROW(KC, KR, OW, NW, BT, EPB)                                                                      \
+  else if (k.C == KC && k.R == KR && k.oneword == OW && k.waves == NW && k.bytetile == BT && k.epb == EPB)   \
+    hipLaunchKernelGGL((pe_step_quad<KC, KR, OW, NW, BT, EPB>), grid, block, lds, s, a);
+      if (false) {
       }
+      PE_QUAD_KERNELS(PE_ROW)
+      else return fail(PE_ERR_ARG, "internal: no such sector kernel");
+#undef PE_ROW
+      break;
+    case StepFamily::fast:
+      if (k.C == 16 && k.oneword)
+        hipLaunchKernelGGL((pe_step_fast<16, 6, true>), grid, block, lds, s, a);
+      else if (k.C == 16)
+        hipLaunchKernelGGL((pe_step_fast<16, 6, false>), grid, block, lds, s, a);
+      else
+        hipLaunchKernelGGL((pe_step_fast<64, 6, false>), grid, block, lds, s, a);
+      break;
+    case StepFamily::wave: {  // pe_step_wave: one wave per env
+      const bool aln = wave_aligned(h->g);
+      if (h->g.WPR == 1) {
+        if (aln)
+          hipLaunchKernelGGL((pe_step_wave<1, true>), grid, block, lds, s, a);
+        else
+          hipLaunchKernelGGL((pe_step_wave<1, false>), grid, block, lds, s, a);
+      } else {
+        if (aln)
+          hipLaunchKernelGGL((pe_step_wave<kCoopWPR, true>), grid, block, lds, s, a);
+        else
+          hipLaunchKernelGGL((pe_step_wave<kCoopWPR, false>), grid, block, lds, s, a);
+      }
+      break;
     }
   }
   PE_HIP(hipGetLastError());
@@ -3074,14 +3003,14 @@ int launch_prefetch(const pe_handle* h, hipStream_t s, int all) {
     hipLaunchKernelGGL(pe_pf_compact_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->pf, h->n);
     PE_HIP(hipGetLastError());
   }
-  const size_t lds = sizeof(float) * (size_t)kTabFloats + 4 * 8 * (size_t)coop_scratch_words(h->g.G, h->g.WPR);
+  const size_t lds = coop_lds_bytes(h->g);
   if (h->g.WPR == 1) {
-    if (h->tile_codes)
+    if (h->k.bytetile)
       hipLaunchKernelGGL((pe_prefetch_kernel<1, true>), grid, block, lds, s, a, all);
     else
       hipLaunchKernelGGL((pe_prefetch_kernel<1, false>), grid, block, lds, s, a, all);
   } else {
-    if (h->tile_codes)
+    if (h->k.bytetile)
       hipLaunchKernelGGL((pe_prefetch_kernel<kCoopWPR, true>), grid, block, lds, s, a, all);
     else
       hipLaunchKernelGGL((pe_prefetch_kernel<kCoopWPR, false>), grid, block, lds, s, a, all);
@@ -3093,7 +3022,7 @@ int launch_prefetch(const pe_handle* h, hipStream_t s, int all) {
 int launch_reset(const pe_handle* h, const StepArgs& a, hipStream_t s) {
   if (h->coop_max_done > 0) {  // the cooperative reset applies (pe_coop.hpp coop_reset_ok)
     dim3 cgrid((unsigned)((h->n + 3) / 4)), cblock(256);
-    const size_t clds = sizeof(float) * (size_t)kTabFloats + 4 * 8 * (size_t)coop_scratch_words(h->g.G, h->g.WPR);
+    const size_t clds = coop_lds_bytes(h->g);
     if (h->g.WPR == 1)
       hipLaunchKernelGGL(pe_reset_coop_kernel<1>, cgrid, cblock, clds, s, a);
     else
@@ -3108,31 +3037,33 @@ int launch_reset(const pe_handle* h, const StepArgs& a, hipStream_t s) {
   return PE_OK;
 }
 
-template <int C, int R>
-bool table_matches(const int8_t* dx, const int8_t* dy) {
-  for (int i = 0; i < C; ++i)
-    for (int r = 0; r < R; ++r)
-      if (LidarTab<C, R>::dx[i][r] != dx[i * R + r] || LidarTab<C, R>::dy[i][r] != dy[i * R + r]) return false;
-  return true;
-}
-
-const char* variant_name(int v) {
-  switch (v) {
-    case V_C16R6_1W: return "pe_step_fast<C16,R6,1word>";
-    case V_C16R6: return "pe_step_fast<C16,R6>";
-    case V_C64R6: return "pe_step_fast<C64,R6>";
-    case V_QUAD_C16R6_1W: return "pe_step_quad<C16,R6,1word>";
-    case V_QUAD_C16R6: return "pe_step_quad<C16,R6>";
-    case V_QUAD_C64R6: return "pe_step_quad<C64,R6>";
-    case V_QUAD_C10R2_1W: return "pe_step_quad<C10,R2,1word>";
-    case V_QUAD_C10R2: return "pe_step_quad<C10,R2>";
-    case V_QUAD_C16R4_1W: return "pe_step_quad<C16,R4,1word>";
-    case V_QUAD_C16R4: return "pe_step_quad<C16,R4>";
-    case V_QUAD_RT_1W: return "pe_step_quad<runtime C,R,1word>";
-    case V_QUAD_RT: return "pe_step_quad<runtime C,R>";
-    case V_FAR_C64R32: return "pe_step_far<C64,R32>";
-    default: return "pe_step_wave";
+// Everything a handle owns, freed, with its device bound by the caller: pe_destroy, and the
+// owner of a handle that pe_create does not finish.
+int free_handle(pe_handle* h) {
+  int rc = PE_OK;
+  if (h->mem) {
+    hipError_t e = hipFree(h->mem);
+    if (e != hipSuccess) rc = hip_fail(e, "hipFree");
   }
+  if (h->cur_mem) (void)hipFree(h->cur_mem);
+  if (h->pf_mem) (void)hipFree(h->pf_mem);
+  pe_internal_render_free(h);
+  delete h;
+  return rc;
+}
+struct HandleDeleter {
+  void operator()(pe_handle* h) const { (void)free_handle(h); }
+};
+
+// make_plan() with this build's knobs; a rejection recorded for pe_last_error()
+int plan_for(const pe_config& c, int n_envs, int num_cus, Plan& p) {
+#ifdef PE_DEBUG_KNOBS
+  const Knobs kb = knobs_from_env();
+#else
+  const Knobs kb;
+#endif
+  const PlanError e = make_plan(c, n_envs, num_cus, kb, p);
+  return e.code == PE_OK ? PE_OK : fail(e.code, e.msg);
 }
 
 }  // namespace
@@ -3170,461 +3101,127 @@ const char* pe_last_error(void) { return g_err.c_str(); }
 
 int pe_internal_set_error(int code, const char* msg) { return fail(code, msg); }
 
+int pe_internal_plan(const pe_config* c, int32_t n_envs, int32_t num_cus, pe_plan_info* out) {
+  if (!c || !out) return fail(PE_ERR_ARG, "null argument");
+  Plan p;
+  if (const int rc = plan_for(*c, n_envs, num_cus, p)) return rc;
+  std::memset(out, 0, sizeof(*out));
+  out->variant = kernel_variant(p.k);
+  std::memcpy(out->kernel_name, p.kname, sizeof(out->kernel_name));
+  out->tile_codes = p.k.bytetile ? 1 : 0;
+  out->stagger = p.stagger;
+  out->quad_epb = p.k.epb;
+  out->quad_waves = p.k.waves;
+  out->coop_max_done = p.coop_max_done;
+  out->prefetch_every = p.pf_every;
+  out->state_bytes = p.mem.bytes;
+  out->prefetch_bytes = p.pf.bytes;
+  return PE_OK;
+}
+
+// Plan (pe_plan.hpp: every argument check and every choice, no device), bind the device,
+// allocate, build and upload the tables, reset, publish.  A return before the last line leaves
+// what was allocated to `owner`.
 int pe_create(const pe_config* c, int32_t device, int32_t n_envs, pe_handle** out) {
   if (!c || !out) return fail(PE_ERR_ARG, "null argument");
   *out = nullptr;
-  if (c->abi_version != PE_ABI_VERSION) return fail(PE_ERR_ARG, "ABI version mismatch");
-  const int G = c->grid_size, R = c->lidar_range, C = c->lidar_channels, P = c->num_plants, O = c->num_obstacles;
-  if (G < 1 || G > 128) return fail(PE_ERR_ARG, "grid_size must be in [1, 128]");
-  if (R < 1 || R > 64) return fail(PE_ERR_ARG, "lidar_range must be in [1, 64]");
-  if (C < 1 || C > 256) return fail(PE_ERR_ARG, "lidar_channels must be in [1, 256]");
-  if (P < 0 || P >= G * G) return fail(PE_ERR_ARG, "num_plants must be in [0, G*G)");
-  if (O < 0) return fail(PE_ERR_ARG, "num_obstacles must be >= 0");
-  if (O / 3 > 0 && G < 5) return fail(PE_ERR_ARG, "randint(2, G-3) needs grid_size >= 5 (plantos_env.py:344)");
-  if (c->max_steps < 1 || c->max_steps > 65535) return fail(PE_ERR_ARG, "max_steps must be in [1, 65535]");
-  if (c->map_generation_algo != PE_MAP_ORIGINAL && c->map_generation_algo != PE_MAP_MAZE)
-    return fail(PE_ERR_ARG, "map_generation_algo must be PE_MAP_ORIGINAL or PE_MAP_MAZE");
-  if (c->map_generation_algo == PE_MAP_MAZE && G < 7)
-    return fail(PE_ERR_ARG, "the maze needs grid_size >= 7 (randint(0, (G-1)//6 - 1), plantos_env_new.py:427)");
-  if (n_envs < 1) return fail(PE_ERR_ARG, "n_envs must be >= 1");
-  if (2 * (G + 2 * R) > 64 * kMaxWPR) return fail(PE_ERR_ARG, "G + 2R too large");
-
+  // (the CU count is the plan's one input from the device: read before it, so that a rejected
+  // config never binds a device)
   int ndev = 0;
-  hipError_t he = hipGetDeviceCount(&ndev);
-  if (he != hipSuccess || ndev == 0) return fail(PE_ERR_DEVICE, "no HIP device available (no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(PE_ERR_ARG, "bad device index");
-  (void)hipGetLastError();  // stale error of an earlier call (see DeviceGuard)
-  struct Restore {
-    int prev = -1;
-    ~Restore() {
-      if (prev >= 0) (void)hipSetDevice(prev);
-    }
-  } restore;
-  PE_HIP(hipGetDevice(&restore.prev));
-  PE_HIP(hipSetDevice(device));
+  const bool have_dev = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+  const bool dev_ok = have_dev && device >= 0 && device < ndev;
   hipDeviceProp_t prop;
-  PE_HIP(hipGetDeviceProperties(&prop, device));
+  std::memset(&prop, 0, sizeof(prop));
+  if (dev_ok) PE_HIP(hipGetDeviceProperties(&prop, device));
+  Plan p;
+  if (const int rc = plan_for(*c, n_envs, prop.multiProcessorCount, p)) return rc;
+  if (!have_dev) return fail(PE_ERR_DEVICE, "no HIP device available (no CPU fallback)");
+  if (!dev_ok) return fail(PE_ERR_ARG, "bad device index");
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(PE_ERR_DEVICE, std::string("built for gfx950, device is ") + prop.gcnArchName);
+  DeviceGuard dg(device);  // (also drops a stale error of an earlier call)
+  if (dg.rc) return dg.rc;
 
-  pe_handle* h = new (std::nothrow) pe_handle();
+  std::unique_ptr<pe_handle, HandleDeleter> owner(new (std::nothrow) pe_handle());
+  pe_handle* h = owner.get();
   if (!h) return fail(PE_ERR_NOMEM, "host allocation failed");
   h->device = device;
   h->n = n_envs;
   h->cfg = *c;
-  Geo& g = h->g;
-  g.G = G;
-  g.C = C;
-  g.R = R;
-  g.D = 5 * C + 27;
-  g.DS = g.D | 1;
-  g.GG = G * G;
-  g.WPR = (2 * (G + 2 * R) + 63) / 64;
-  // visit row words: the padded row's G+4 nibbles + a spare word, so that the 8-nibble
-  // window starting at any padded column y-1 (words vw, vw+1) stays inside the row.
-  // (Tried: 4 words up to G = 25 -- 16-B rows, one load per window row in the
-  // multi-word kernel: 25x25 10.38 -> 10.97 us, 21x21/C10/R2 one-word 8.05 -> 8.14;
-  // profiles/r3j_ab_*.jsonl.)
-  g.NW = (4 * (G + 4) + 31) / 32 + 1;
-  if (g.NW < 4) g.NW = 4;  // 16-B visit rows: one dwordx4 per row in the sector kernel
-  g.EW = (g.GG + 31) / 32;
-  g.gstride = (int64_t)align_up((size_t)G * g.WPR, 2);  // 16-B aligned env blocks (row-pair loads)
-  // two visit slots per env, 16-B aligned (episode k's visits in slot k & 1: pe_device.hpp vis_env)
-  g.vslot = (int64_t)align_up((size_t)G * g.NW, 4);
-  g.vstride = 2 * g.vslot;
-  g.hstride = (int64_t)align_up((size_t)g.GG, 8);
-  // explored words; also the picks scratch of a curriculum reset that keeps visits
-  g.estride = (int64_t)align_up((size_t)std::max(g.EW, (P + 1) / 2), 4);
-  // LDS limits: the lane-per-env kernels that every geometry keeps (pe_load_maps_kernel,
-  // and pe_reset_kernel where the cooperative reset does not apply) hold a [64 x D]
-  // obs tile -- this caps C at 120 whatever the step kernel; the one-wave-per-env step
-  // kernel (the step kernel of every geometry without a sector kernel) its header +
-  // 8 per-wave regions.
-  if (lds_bytes(g) > 160 * 1024) {
-    delete h;
-    return fail(PE_ERR_ARG, "observation tile does not fit LDS (lidar_channels <= 120)");
-  }
-  if (sizeof(float) * ((size_t)wave_hdr_floats(C, R, wave_aln_ok(G, R, g.WPR)) + kWaveEnvs * (size_t)wave_lds_floats(G, R, g.WPR, g.NW, g.D)) >
-      160 * 1024) {
-    delete h;
-    return fail(PE_ERR_ARG, "the one-wave-per-env step kernel's window does not fit LDS");
-  }
-
-  Rules& rl = h->rl;
-  rl.r_goal = c->r_goal;
-  rl.r_mistake = c->r_mistake;
-  rl.r_invalid = c->r_invalid;
-  rl.r_water_empty = c->r_water_empty;
-  rl.r_step = c->r_step;
-  rl.r_exploration = c->r_exploration;
-  rl.r_revisit = c->r_revisit;
-  rl.r_complete = c->r_complete;
-  rl.p_thirsty = c->thirsty_plant_prob;
-  rl.seed = c->seed;
-  rl.env_off = c->env_id_offset;
-  rl.P = P;
-  rl.O = O;
-  rl.map_algo = c->map_generation_algo;
-  // Auto-resets in the step kernel: wave-cooperative (pe_coop.hpp: one env at a
-  // time per wave, ~10 us each at 20x20) when a block has few done envs; one lane
-  // per env (all of a wave's envs at once, ~0.26 ms for a whole batch at 20x20)
-  // when many are done together -- unless the lane path would have to scan its
-  // grid image in HBM (no room for it in the obs-tile row), where it is ~30x
-  // slower (29 ms for a whole 64x64 batch) and the cooperative path always wins.
-  if (!coop_reset_ok(G, R, g.WPR, g.NW, P, C, c->map_generation_algo))
-    h->coop_max_done = 0;
-  else if (reset_scratch_bytes(G, g.WPR, P) <= 4 * g.D)
-    h->coop_max_done = kCoopMaxDone;
-  else
-    h->coop_max_done = kQuadEnvs;
-  rl.max_steps = c->max_steps;
-
-  // host tables
-  Tables tab;
-  std::memset(&tab, 0, sizeof(tab));
-  for (int r = 0; r <= R; ++r) tab.dist[r] = (float)((double)r / (double)R);
-  for (int x = 0; x < G; ++x) tab.pos[x] = (float)((double)x / (double)G);
-  for (int v = 0; v < 16; ++v) tab.vis[v] = (float)((double)(v < 10 ? v : 10) / 10.0);
-  for (int p = 0; p < G + 2 * R; ++p) {
-    int w = (2 * p) / 64, b = (2 * p) % 64;
-    if (p < R || p >= G + R)
-      tab.grid_pad[w] |= 1ull << b;
-    else
-      tab.grid_real[w] |= 1ull << b;
-  }
-  for (int p = 0; p < G + 4; ++p)
-    if (p < 2 || p >= G + 2) tab.vis_pad[(4 * p) / 32] |= 10u << ((4 * p) % 32);
-  const size_t nl = (size_t)C * R;
-  int8_t* ldx = new int8_t[nl];
-  int8_t* ldy = new int8_t[nl];
-  const double pi = 3.141592653589793;  // math.pi; plantos_env.py:261-267
-  for (int i = 0; i < C; ++i) {
-    double angle = ((2.0 * pi) * (double)i) / (double)C;
-    for (int r = 1; r <= R; ++r) {
-      ldx[i * R + r - 1] = (int8_t)(int)((double)r * std::cos(angle));
-      ldy[i * R + r - 1] = (int8_t)(int)((double)r * std::sin(angle));
-    }
-  }
-  h->variant = V_GENERIC;
-  if (C == 16 && R == 6 && table_matches<16, 6>(ldx, ldy)) h->variant = g.WPR == 1 ? V_C16R6_1W : V_C16R6;
-  if (C == 64 && R == 6 && table_matches<64, 6>(ldx, ldy)) h->variant = V_C64R6;
-  // A/B knobs of the measurement tools (tools/ab_build.sh builds a SEPARATE library
-  // with -DPE_DEBUG_KNOBS); the product library reads no environment variable.
-  bool lane_kernels = false;
-  h->quad_waves = 4;  // measured best at C=16 and C=64 (profiles/r1c-r1e); 8: the 16-env shape below
-  h->stagger = 0;
-  h->lds_floor = 0;
-#ifdef PE_DEBUG_KNOBS
-  if (const char* kenv = std::getenv("PE_STEP_KERNEL")) lane_kernels = std::strcmp(kenv, "lane") == 0;
-  if (const char* sg = std::getenv("PE_STAGGER")) h->stagger = std::atoi(sg);
-  if (const char* lf = std::getenv("PE_LDS_FLOOR")) h->lds_floor = std::min<size_t>(std::strtoul(lf, nullptr, 10), 160 * 1024);
-#endif
-  if (!lane_kernels && h->variant != V_GENERIC) h->variant += V_QUAD_C16R6_1W - V_C16R6_1W;
-  // sector kernels of the other specialized geometries (4 waves; no lane-kernel twin)
-  if (!lane_kernels && C == 10 && R == 2 && table_matches<10, 2>(ldx, ldy)) h->variant = V_QUAD_C10R2_1W;
-  if (!lane_kernels && C == 16 && R == 4 && table_matches<16, 4>(ldx, ldy)) h->variant = V_QUAD_C16R4_1W;
-  // R > 14 with a compile-time table: the far sector kernel (its rows and the auto-reset
-  // path's are kCoopWPR words: 96 < G + 2R <= 128)
-  if (!lane_kernels && C == 64 && R == 32 && g.WPR == kCoopWPR && table_matches<64, 32>(ldx, ldy))
-    h->variant = V_FAR_C64R32;
-  // the one-word form (whole padded row in one u64) needs WPR == 1 and 16-B visit
-  // rows (NW == 4: G <= 20); otherwise the multi-word (funnel-shifted) form
-  const bool oneword = g.WPR == 1 && g.NW == 4;
-  if ((h->variant == V_QUAD_C10R2_1W || h->variant == V_QUAD_C16R4_1W) && !oneword) h->variant += 1;
-  // every other geometry with 4 <= C <= 32 and 2 <= R <= 14: the sector kernel with
-  // table-driven rays (quad_rays_rt) instead of one wave per env -- 64 envs per
-  // workgroup share the per-env work the wave kernel repeats per wave
-  // (33 <= C <= 64: with the byte-coded tile, below)
-  if (!lane_kernels && h->variant == V_GENERIC && C >= 4 && C <= kRtCMaxBT && R >= 2 && R <= kRtRMax)
-    h->variant = oneword ? V_QUAD_RT_1W : V_QUAD_RT;
-  // (V_QUAD_C16R6_1W has 16-B visit rows: WPR == 1 at R = 6 means 2 (G + 12) <= 64, so G <= 20 and NW == 4)
-  // byte-coded obs tile where the f32 tile limits the sector kernel's occupancy
-  // (C = 64: 89 KB -> 22 KB of LDS per workgroup)
-  h->tile_codes = h->variant == V_QUAD_C64R6 || is_far(h->variant) ||
-                          (is_quad(h->variant) && h->variant >= V_QUAD_RT_1W && C > kRtCMax)
-                      ? 1 : 0;
-  // the runtime kernel with C <= 32 too, where its f32 tile holds fewer workgroups per CU than
-  // the byte tile and the batch needs more than one round of them (32x32 / C24 / R9: 54 KB, two
-  // per CU -- 65536 envs ran as two waves of workgroups, the second starting ~13 us in,
-  // profiles/r5s/stamps_g32.json); small batches keep the f32 tile (no expansion at the store)
-  if (!h->tile_codes && is_quad(h->variant) && h->variant >= V_QUAD_RT_1W) {
-    auto per_cu = [](size_t l) { return std::min<size_t>(4, (size_t)160 * 1024 / l); };
-    const size_t lf = quad_lds_bytes(g, false, true), lb = quad_lds_bytes(g, true, true);
-    const int64_t blocks = ((int64_t)n_envs + kQuadEnvs - 1) / kQuadEnvs;
-    if (per_cu(lb) > per_cu(lf) && blocks > (int64_t)prop.multiProcessorCount * (int64_t)per_cu(lf)) h->tile_codes = 1;
-  }
-#ifdef PE_DEBUG_KNOBS
-  if (const char* tc = std::getenv("PE_TILE_CODES"))
-    if (h->variant == V_QUAD_C16R6_1W) h->tile_codes = std::atoi(tc) != 0;
-#endif
-  // obs as byte codes at the boundary (pe_step_codes): the byte-coded tile kernels
-  h->obs_codes = c->obs_codes ? 1 : 0;
-  if (h->obs_codes) {
-    if (!(h->variant == V_QUAD_C16R6_1W || h->variant == V_QUAD_C64R6 || h->variant == V_QUAD_RT_1W ||
-          h->variant == V_QUAD_RT || is_far(h->variant))) {
-      delete[] ldx;
-      delete[] ldy;
-      delete h;
-      return fail(PE_ERR_ARG, "obs_codes needs a byte-coded sector kernel (C=16/R=6 with G<=20, C=64/R=6, or "
-                              "4<=C<=64 with 2<=R<=14 and no compile-time kernel)");
-    }
-    h->tile_codes = 1;
-  }
-  if (h->tile_codes) {
-    // (not the byte-coded C16 kernel -- config 5's codes step: its quarters started apart
-    // cost it ~0.9 us desynchronized, 11.68 -> 10.75 us without, profiles/r6c/ab_codesstag;
-    // the runtime byte-tile kernel keeps it: 32x32/C24/R9 17.0 -> 18.1 us without)
-    // all 1024 workgroups of a 65536-env batch are resident at once (4 per CU) and
-    // would run their load, compute and 89-KB store phases in lockstep: starting the
-    // grid's quarters ~0.85 us apart overlaps one quarter's stores with the next
-    // one's loads (64x64 / 64 rays, same-box: 28.7 -> 26.3 us; 2x that: 27.0)
-    // (the far kernel: 8 -- 52.8 -> 52.1 us, desynchronized unchanged, profiles/r6d/ab_farstag)
-    h->stagger = h->variant == V_QUAD_C16R6_1W ? 0 : (is_far(h->variant) ? 8 : 4);
-  }
-#ifdef PE_DEBUG_KNOBS
-  if (const char* sg = std::getenv("PE_STAGGER")) h->stagger = std::atoi(sg);
-#endif
-  if (is_quad(h->variant) && step_lds_bytes(g, h->variant, h->tile_codes) > 160 * 1024)
-    h->variant = h->variant <= V_QUAD_C64R6 ? h->variant - (V_QUAD_C16R6_1W - V_C16R6_1W) : V_GENERIC;
-#ifdef PE_DEBUG_KNOBS
-  if (const char* kenv = std::getenv("PE_STEP_KERNEL"))
-    if (std::strcmp(kenv, "wave") == 0) h->variant = V_GENERIC;  // A/B: the one-wave-per-env kernel
-#endif
-  if (!is_quad(h->variant)) h->tile_codes = 0;
-  if (h->obs_codes && !h->tile_codes) {
-    delete[] ldx;
-    delete[] ldy;
-    delete h;
-    return fail(PE_ERR_ARG, "obs_codes: the byte-coded tile does not fit this geometry");
-  }
-  // envs per workgroup: a batch too small to give every CU four 64-env workgroups
-  // (1024 at 65536 envs) is cut into 16- or 32-env workgroups instead, so that it
-  // still spreads over all 256 CUs (headline geometry's kernel only; 4 waves, f32 tile)
-  // (up to 4096 envs: 8 waves x 16 envs -- two waves per SIMD on every CU, sectors of 2
-  // rays: 2048 envs 4.56 -> 4.41 us, 4096 4.56 -> 4.49; 8192 4.82 -> 4.98 us, kept at 4)
-  h->quad_epb = kQuadEnvs;
-  if (h->variant == V_QUAD_C16R6_1W && !h->tile_codes) {
-    h->quad_epb = n_envs <= kSmallBatch16 ? 16 : (n_envs <= kSmallBatch32 ? 32 : kQuadEnvs);
-    if (n_envs <= kSmallBatch8W) h->quad_waves = 8;
-  }
-#ifdef PE_DEBUG_KNOBS
-  if (const char* ep = std::getenv("PE_QUAD_EPB"))
-    if (h->variant == V_QUAD_C16R6_1W && !h->tile_codes) {
-      const int v = std::atoi(ep);
-      h->quad_epb = v == 16 || v == 32 ? v : kQuadEnvs;
-      if (h->quad_epb != 16) h->quad_waves = 4;  // (the 8-wave kernel exists with 16 envs only)
-    }
-#endif
+  h->g = p.g;
+  h->rl = p.rl;
+  h->k = p.k;
+  h->obs_codes = p.obs_codes;
+  std::memcpy(h->kname, p.kname, sizeof(h->kname));
+  h->lds_floor = p.lds_floor;
+  h->stagger = p.stagger;
   h->num_cus = prop.multiProcessorCount;
-  h->kname = variant_name(h->variant);
-  if (h->quad_epb != kQuadEnvs) {
-    std::snprintf(h->kname_buf, sizeof(h->kname_buf), "%.*s%s,E%d>", (int)std::strlen(h->kname) - 1, h->kname,
-                  h->quad_waves == 8 ? ",W8" : "", h->quad_epb);
-    h->kname = h->kname_buf;
-  } else if (h->tile_codes) {  // the byte-coded tile instantiation (pe_step_quad<..., BT = true>)
-    std::snprintf(h->kname_buf, sizeof(h->kname_buf), "%.*s,bytetile>", (int)std::strlen(h->kname) - 1, h->kname);
-    h->kname = h->kname_buf;
-  }
-  // explicit reset-path tuning (pe_config.coop_max_done; -1: the choice above) --
-  // applied before the prefetch decision, which depends on it
-  if (c->coop_max_done >= 0 && coop_reset_ok(G, R, g.WPR, g.NW, P, C, c->map_generation_algo))
-    h->coop_max_done = std::min(c->coop_max_done, kQuadEnvs);
-  // Prefetched resets (pe_coop.hpp Prefetch) where the sector kernel takes the
-  // cooperative path.  The done-count threshold above stays: a whole block done at
-  // once (a synchronized batch truncating) is cheaper through the lane-per-env path,
-  // which consumes no record and so queues no regeneration (20x20: 0.26 ms per
-  // batch reset, against 0.09 ms for the copies + ~0.3 ms to regenerate 65536 maps).
-  h->pf_every = c->prefetch_every >= 0 ? c->prefetch_every : kPrefetchEvery;
-  if (!(is_quad(h->variant) || h->variant == V_GENERIC) || h->coop_max_done <= 0 || !c->autoreset) h->pf_every = 0;
+  h->coop_max_done = p.coop_max_done;
+  h->pf_every = p.pf_every;
+  h->bytes = p.mem.bytes;
 
-  // one device allocation carved into 256-B aligned arrays
-  const size_t n = (size_t)n_envs;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  const size_t o_tab = carve(sizeof(Tables));
-  const size_t o_ldx = carve(nl), o_ldy = carve(nl);
-  const int RP = (R + 7) & ~7;
-  const bool wave_aln = h->variant == V_GENERIC && wave_aln_ok(G, R, g.WPR);  // pe_step_wave<., true>
-  const bool rt_tab = h->variant == V_QUAD_RT_1W || h->variant == V_QUAD_RT;  // u32 probe entries (quad_rays_rt)
-  // (rt_tab: the LDS-form entries, then the register-window header [4][4] and entries, pe_quad.hpp)
-  const size_t o_ldxy = carve(wave_aln ? ((size_t)C * RP * 3 + 15) & ~(size_t)15
-                                       : (rt_tab ? (2 * (size_t)C * RP + 16) * 4 : (size_t)C * RP * 2));
-  const size_t o_err = carve(sizeof(uint32_t));
-  const size_t o_scal = carve(n * sizeof(uint4));
-  const size_t o_ret = carve(n * sizeof(double));
-  const size_t o_grid = carve(n * (size_t)g.gstride * 8);
-  const size_t o_vis = carve(n * (size_t)g.vstride * 4);
-  const size_t o_vx = carve(n * (size_t)g.hstride * 4);
-  const size_t o_vpend = carve(n * sizeof(uint32_t));
-  const size_t o_expl = carve(n * (size_t)g.estride * 4);
-  h->bytes = off;
-  if (is_far(h->variant)) {
-    // pe_step_far loads a quadrant's off-map rows UNCLAMPED (pe_far.hpp far_sector: up to
-    // R rows before the env's grid block and R rows + one raw word after it, selected away
-    // afterwards): the first env's must land in the arrays carved before the grid, the last
-    // env's in those after it -- inside this one allocation
-    const size_t row_b = (size_t)kFarRow32 * 4, grid_end = o_grid + n * (size_t)g.gstride * 8;
-    if (g.WPR != kCoopWPR || o_grid < (size_t)R * row_b || h->bytes - grid_end < (size_t)(R + 1) * row_b) {
-      delete[] ldx;
-      delete[] ldy;
-      delete h;
-      return fail(PE_ERR_ARG, "pe_step_far: the allocation leaves less than R padded grid rows of slack around the "
-                              "grid array (its off-map row loads would leave the allocation)");
-    }
-  }
-  hipError_t me = hipMalloc(&h->mem, h->bytes);
-  if (me != hipSuccess) {
-    delete[] ldx;
-    delete[] ldy;
-    delete h;
-    return fail(PE_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(me));
-  }
+  const StateLayout& m = p.mem;
+  hipError_t me = hipMalloc(&h->mem, m.bytes);
+  if (me != hipSuccess) return fail(PE_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(me));
   char* base = static_cast<char*>(h->mem);
-  h->st.tab = reinterpret_cast<const Tables*>(base + o_tab);
-  h->st.ldx = reinterpret_cast<const signed char*>(base + o_ldx);
-  h->st.ldy = reinterpret_cast<const signed char*>(base + o_ldy);
-  h->st.ldxy = reinterpret_cast<const int16_t*>(base + o_ldxy);
-  h->st.err_bits = reinterpret_cast<uint32_t*>(base + o_err);
-  h->st.scal = reinterpret_cast<uint4*>(base + o_scal);
-  h->st.ep_ret = reinterpret_cast<double*>(base + o_ret);
-  h->st.grid = reinterpret_cast<uint64_t*>(base + o_grid);
-  h->st.vis = reinterpret_cast<uint32_t*>(base + o_vis);
-  h->st.vx = reinterpret_cast<uint32_t*>(base + o_vx);
-  h->st.vpend = reinterpret_cast<uint32_t*>(base + o_vpend);
-  h->st.expl = reinterpret_cast<uint32_t*>(base + o_expl);
-  int rc = PE_OK;
-  if (h->pf_every > 0) {
-    size_t po = 0;
-    auto pcarve = [&](size_t bytes) {
-      size_t o = po;
-      po = align_up(po + bytes, 256);
-      return o;
-    };
-    const size_t p_scal = pcarve(n * sizeof(uint4)), p_grid = pcarve(n * (size_t)g.gstride * 8);
-    const uint32_t ostride = (uint32_t)pf_ostride(g, h->tile_codes);
-    const size_t p_obs = pcarve(n * (size_t)ostride), p_q = pcarve(n * 4), p_qn = pcarve(2 * 4);
-    const size_t p_flag = pcarve(n);
-    if (hipMalloc(&h->pf_mem, po) != hipSuccess || hipMemset(h->pf_mem, 0, po) != hipSuccess) {
-      if (h->pf_mem) (void)hipFree(h->pf_mem);
-      (void)hipFree(h->mem);
-      delete[] ldx;
-      delete[] ldy;
-      delete h;
+  h->st.tab = reinterpret_cast<const Tables*>(base + m.tab);
+  h->st.ldx = reinterpret_cast<const signed char*>(base + m.ldx);
+  h->st.ldy = reinterpret_cast<const signed char*>(base + m.ldy);
+  h->st.ldxy = reinterpret_cast<const int16_t*>(base + m.ldxy);
+  h->st.err_bits = reinterpret_cast<uint32_t*>(base + m.err);
+  h->st.scal = reinterpret_cast<uint4*>(base + m.scal);
+  h->st.ep_ret = reinterpret_cast<double*>(base + m.ret);
+  h->st.grid = reinterpret_cast<uint64_t*>(base + m.grid);
+  h->st.vis = reinterpret_cast<uint32_t*>(base + m.vis);
+  h->st.vx = reinterpret_cast<uint32_t*>(base + m.vx);
+  h->st.vpend = reinterpret_cast<uint32_t*>(base + m.vpend);
+  h->st.expl = reinterpret_cast<uint32_t*>(base + m.expl);
+  if (p.pf_every > 0) {
+    const PrefetchLayout& f = p.pf;
+    if (hipMalloc(&h->pf_mem, f.bytes) != hipSuccess || hipMemset(h->pf_mem, 0, f.bytes) != hipSuccess)
       return fail(PE_ERR_NOMEM, "prefetch buffers: hipMalloc failed");
-    }
     char* pb = static_cast<char*>(h->pf_mem);
-    h->pf.scal = reinterpret_cast<uint4*>(pb + p_scal);
-    h->pf.grid = reinterpret_cast<uint64_t*>(pb + p_grid);
-    h->pf.obs = reinterpret_cast<float*>(pb + p_obs);
-    h->pf.ostride = ostride;
-    h->pf.queue = reinterpret_cast<uint32_t*>(pb + p_q);
-    h->pf.qn = reinterpret_cast<uint32_t*>(pb + p_qn);
-    h->pf.flag = reinterpret_cast<uint8_t*>(pb + p_flag);
-    const size_t plds = sizeof(float) * (size_t)kTabFloats + 4 * 8 * (size_t)coop_scratch_words(G, g.WPR);
+    h->pf.scal = reinterpret_cast<uint4*>(pb + f.scal);
+    h->pf.grid = reinterpret_cast<uint64_t*>(pb + f.grid);
+    h->pf.obs = reinterpret_cast<float*>(pb + f.obs);
+    h->pf.ostride = f.ostride;
+    h->pf.queue = reinterpret_cast<uint32_t*>(pb + f.queue);
+    h->pf.qn = reinterpret_cast<uint32_t*>(pb + f.qn);
+    h->pf.flag = reinterpret_cast<uint8_t*>(pb + f.flag);
+    // the queue-mode prefetch grid: every workgroup the chip holds at once (launch_prefetch)
     int per_cu = 0;
-    hipError_t oe = g.WPR == 1
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pe_prefetch_kernel<1, false>, 256, plds)
-        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pe_prefetch_kernel<kCoopWPR, false>, 256, plds);
+    hipError_t oe = h->g.WPR == 1
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pe_prefetch_kernel<1, false>, 256, coop_lds_bytes(h->g))
+        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pe_prefetch_kernel<kCoopWPR, false>, 256,
+                                                       coop_lds_bytes(h->g));
     if (oe != hipSuccess || per_cu < 1) per_cu = 1;
     h->pf_blocks = per_cu * prop.multiProcessorCount;
   }
-  hipError_t e1 = hipMemset(h->mem, 0, h->bytes);
-  hipError_t e2 = hipMemcpy(base + o_tab, &tab, sizeof(Tables), hipMemcpyHostToDevice);
-  hipError_t e3 = hipMemcpy(base + o_ldx, ldx, nl, hipMemcpyHostToDevice);
-  hipError_t e4 = hipMemcpy(base + o_ldy, ldy, nl, hipMemcpyHostToDevice);
-  std::vector<int16_t> ldxy((size_t)C * RP, 0);
-  for (int i = 0; i < C; ++i)
-    for (int r = 0; r < R; ++r)
-      ldxy[(size_t)i * RP + r] = (int16_t)((uint8_t)ldx[i * R + r] | ((int)ldy[i * R + r] << 8));
-  hipError_t e5;
-  if (wave_aln) {  // pe_step_wave<., true>'s LDS header entries: [C][RP] u16 byte offsets into
-                   // the aligned window, then [C][RP] u8 bit shifts
-    std::vector<uint8_t> aln(((ldxy.size() * 3 + 15) & ~(size_t)15), 0);
-    for (size_t k = 0; k < ldxy.size(); ++k) {
-      const uint32_t en = aln_entry((uint16_t)ldxy[k], R, (4 * R + 33) >> 5);
-      const uint16_t off = (uint16_t)(4u * (en & 0x7FFu));
-      std::memcpy(aln.data() + 2 * k, &off, 2);
-      aln[2 * ldxy.size() + k] = (uint8_t)((en >> 11) & 31u);
-    }
-    e5 = hipMemcpy(base + o_ldxy, aln.data(), aln.size(), hipMemcpyHostToDevice);
-  } else if (rt_tab) {  // the runtime sector kernel's entries (pe_quad.hpp quad_rays_rt): the probe's LDS
-                        // byte offset from the rover row (dx rows of 64 envs x 8 B) | its bit shift 2(dy+R) << 16
-    std::vector<uint32_t> rt(2 * (size_t)C * RP + 16, 0u);
-    for (int i = 0; i < C; ++i)
-      for (int r = 0; r < R; ++r)
-        rt[(size_t)i * RP + r] = (uint32_t)(uint16_t)(int16_t)(ldx[i * R + r] * kQuadEnvs * 8) |
-                                 ((uint32_t)(2 * (ldy[i * R + r] + R)) << 16);
-    // the register-window form (pe_quad.hpp quad_rays_rt_reg): per wave w (rays [wC/4, (w+1)C/4))
-    // the header {LO, DLO, NROWS, ok}, per probe (dx - LO) | 2(dy - DLO) << 8
-    uint32_t* hdr = rt.data() + (size_t)C * RP;
-    uint32_t* ent = hdr + 16;
-    for (int w = 0; w < 4; ++w) {
-      const int i0 = w * C / 4, i1 = (w + 1) * C / 4;
-      int lo = 1 << 20, hi = -(1 << 20), dlo = 1 << 20, dhi = -(1 << 20);
-      for (int i = i0; i < i1; ++i)
-        for (int r = 0; r < R; ++r) {
-          lo = std::min(lo, (int)ldx[i * R + r]);
-          hi = std::max(hi, (int)ldx[i * R + r]);
-          dlo = std::min(dlo, (int)ldy[i * R + r]);
-          dhi = std::max(dhi, (int)ldy[i * R + r]);
-        }
-      const bool ok = i1 > i0 && hi - lo + 1 <= kRtRegRows && dhi - dlo + 1 <= 16;
-      hdr[4 * w] = (uint32_t)lo;
-      hdr[4 * w + 1] = (uint32_t)dlo;
-      hdr[4 * w + 2] = (uint32_t)(hi - lo + 1);
-      hdr[4 * w + 3] = ok ? 1u : 0u;
-      if (ok)
-        for (int i = i0; i < i1; ++i)
-          for (int r = 0; r < R; ++r)
-            ent[(size_t)i * RP + r] = (uint32_t)(ldx[i * R + r] - lo) | ((uint32_t)(2 * (ldy[i * R + r] - dlo)) << 8);
-    }
-    e5 = hipMemcpy(base + o_ldxy, rt.data(), rt.size() * 4, hipMemcpyHostToDevice);
-  } else {
-    e5 = hipMemcpy(base + o_ldxy, ldxy.data(), ldxy.size() * 2, hipMemcpyHostToDevice);
-  }
-  delete[] ldx;
-  delete[] ldy;
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess) {
-    if (h->pf_mem) (void)hipFree(h->pf_mem);
-    (void)hipFree(h->mem);
-    delete h;
+
+  const Tables tab = make_tables(h->g);
+  const std::vector<uint8_t> ldxy = ray_table(p.ray_tab, h->g.C, h->g.R, p.ldx, p.ldy);
+  if (ldxy.size() != ray_table_bytes(p.ray_tab, h->g.C, h->g.R)) return fail(PE_ERR_ARG, "internal: ray table size");
+  if (hipMemset(h->mem, 0, m.bytes) != hipSuccess ||
+      hipMemcpy(base + m.tab, &tab, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(base + m.ldx, p.ldx.data(), p.ldx.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(base + m.ldy, p.ldy.data(), p.ldy.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(base + m.ldxy, ldxy.data(), ldxy.size(), hipMemcpyHostToDevice) != hipSuccess)
     return fail(PE_ERR_DEVICE, "initial upload failed");
-  }
   // every env starts reset (episode 0), like DummyVecEnv.reset() before the first step
-  StepArgs a = base_args(h);
-  rc = launch_reset(h, a, nullptr);
-  if (rc == PE_OK && h->pf_every > 0) rc = launch_prefetch(h, nullptr, 1);
-  if (rc == PE_OK) {
-    hipError_t se = hipDeviceSynchronize();
-    if (se != hipSuccess) rc = hip_fail(se, "initial reset");
-  }
-  if (rc != PE_OK) {
-    if (h->pf_mem) (void)hipFree(h->pf_mem);
-    (void)hipFree(h->mem);
-    delete h;
-    return rc;
-  }
-  *out = h;
+  if (const int rc = launch_reset(h, base_args(h), nullptr)) return rc;
+  if (h->pf_every > 0)
+    if (const int rc = launch_prefetch(h, nullptr, 1)) return rc;
+  hipError_t se = hipDeviceSynchronize();
+  if (se != hipSuccess) return hip_fail(se, "initial reset");
+  *out = owner.release();
   return PE_OK;
 }
 
 int pe_destroy(pe_handle* h) {
   if (!h) return PE_OK;
   DeviceGuard dg(h);
-  int rc = dg.rc;
-  if (rc == PE_OK && h->mem) {
-    hipError_t e = hipFree(h->mem);
-    if (e != hipSuccess) rc = hip_fail(e, "hipFree");
-  }
-  if (h->cur_mem) (void)hipFree(h->cur_mem);
-  if (h->pf_mem) (void)hipFree(h->pf_mem);
-  pe_internal_render_free(h);
-  delete h;
-  return rc;
+  const int rc = free_handle(h);
+  return dg.rc ? dg.rc : rc;
 }
 
 int pe_curriculum_enable(pe_handle* h, double initial_threshold, double max_threshold, double threshold_increment,
@@ -3722,10 +3319,11 @@ int pe_reset(pe_handle* h, const uint8_t* mask, float* obs, void* stream) {
   return launch_prefetch(h, static_cast<hipStream_t>(stream), 1);  // the new episodes' next maps
 }
 
-int pe_step(pe_handle* h, const void* actions, int32_t action_bytes, float* obs, float* reward, uint8_t* terminated,
-            uint8_t* truncated, float* terminal_obs, double* ep_ret, int32_t* ep_len, int32_t* terminal_info,
-            void* stream) {
-  if (!h || !actions || !obs || !reward || !terminated || !truncated) return fail(PE_ERR_ARG, "null argument");
+// pe_step / pe_step_codes after their argument checks: the step (obs as f32 or as byte codes, the
+// other one NULL), then every pf_every-th call the prefetch of the envs reset since the last one
+static int step_common(pe_handle* h, const void* actions, int32_t action_bytes, float* obs, uint8_t* obs_codes,
+                       float* reward, uint8_t* terminated, uint8_t* truncated, float* terminal_obs, double* ep_ret,
+                       int32_t* ep_len, int32_t* terminal_info, void* stream) {
   if (action_bytes != 4 && action_bytes != 8) return fail(PE_ERR_ARG, "action_bytes must be 4 or 8");
   DeviceGuard dg(h);
   if (dg.rc) return dg.rc;
@@ -3733,6 +3331,7 @@ int pe_step(pe_handle* h, const void* actions, int32_t action_bytes, float* obs,
   a.act_bytes = action_bytes;
   a.actions = actions;
   a.obs = obs;
+  a.obs_codes = obs_codes;
   a.reward = reward;
   a.term = terminated;
   a.trunc = truncated;
@@ -3746,29 +3345,21 @@ int pe_step(pe_handle* h, const void* actions, int32_t action_bytes, float* obs,
   return launch_prefetch(h, static_cast<hipStream_t>(stream), 0);  // maps for the envs reset since the last one
 }
 
+int pe_step(pe_handle* h, const void* actions, int32_t action_bytes, float* obs, float* reward, uint8_t* terminated,
+            uint8_t* truncated, float* terminal_obs, double* ep_ret, int32_t* ep_len, int32_t* terminal_info,
+            void* stream) {
+  if (!h || !actions || !obs || !reward || !terminated || !truncated) return fail(PE_ERR_ARG, "null argument");
+  return step_common(h, actions, action_bytes, obs, nullptr, reward, terminated, truncated, terminal_obs, ep_ret, ep_len,
+                     terminal_info, stream);
+}
+
 int pe_step_codes(pe_handle* h, const void* actions, int32_t action_bytes, uint8_t* obs_codes, float* reward,
                   uint8_t* terminated, uint8_t* truncated, float* terminal_obs, double* ep_ret, int32_t* ep_len,
                   int32_t* terminal_info, void* stream) {
   if (!h || !actions || !obs_codes || !reward || !terminated || !truncated) return fail(PE_ERR_ARG, "null argument");
   if (!h->obs_codes) return fail(PE_ERR_ARG, "pe_step_codes needs a handle created with obs_codes = 1");
-  if (action_bytes != 4 && action_bytes != 8) return fail(PE_ERR_ARG, "action_bytes must be 4 or 8");
-  DeviceGuard dg(h);
-  if (dg.rc) return dg.rc;
-  StepArgs a = base_args(h);
-  a.act_bytes = action_bytes;
-  a.actions = actions;
-  a.obs_codes = obs_codes;
-  a.reward = reward;
-  a.term = terminated;
-  a.trunc = truncated;
-  a.tobs = terminal_obs;
-  a.ep_ret_out = ep_ret;
-  a.ep_len_out = ep_len;
-  a.tinfo = terminal_info;
-  const int rc = launch_step(h, a, static_cast<hipStream_t>(stream));
-  if (rc != PE_OK || h->pf_every <= 0 || ++h->pf_count < h->pf_every) return rc;
-  h->pf_count = 0;
-  return launch_prefetch(h, static_cast<hipStream_t>(stream), 0);
+  return step_common(h, actions, action_bytes, nullptr, obs_codes, reward, terminated, truncated, terminal_obs, ep_ret,
+                     ep_len, terminal_info, stream);
 }
 
 int pe_obs_code_table(const pe_handle* h, float* table) {
@@ -3906,7 +3497,7 @@ int pe_debug_stamps(uint64_t* host, int64_t count) {
 #endif
 
 int32_t pe_num_envs(const pe_handle* h) { return h ? h->n : 0; }
-int32_t pe_kernel_variant(const pe_handle* h) { return h ? h->variant : -1; }
+int32_t pe_kernel_variant(const pe_handle* h) { return h ? kernel_variant(h->k) : -1; }
 const char* pe_kernel_name(const pe_handle* h) { return h ? h->kname : ""; }
 int32_t pe_prefetch_every(const pe_handle* h) { return h ? h->pf_every : 0; }
 uint64_t pe_state_bytes(const pe_handle* h) { return h ? (uint64_t)h->bytes : 0; }

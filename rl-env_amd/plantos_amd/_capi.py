@@ -87,6 +87,16 @@ class PEPolicyLstm(ctypes.Structure):
     ]
 
 
+class PEPlanInfo(ctypes.Structure):
+    """pe_plan_info (csrc/pe_handle.hpp): what pe_create would decide, without a device."""
+    _fields_ = [
+        ("variant", ctypes.c_int32), ("kernel_name", ctypes.c_char * 64), ("tile_codes", ctypes.c_int32),
+        ("stagger", ctypes.c_int32), ("quad_epb", ctypes.c_int32), ("quad_waves", ctypes.c_int32),
+        ("coop_max_done", ctypes.c_int32), ("prefetch_every", ctypes.c_int32), ("state_bytes", ctypes.c_uint64),
+        ("prefetch_bytes", ctypes.c_uint64),
+    ]
+
+
 class PlantOSNativeError(RuntimeError):
     pass
 
@@ -135,6 +145,9 @@ def lib():
     L.pe_kernel_name.restype = ctypes.c_char_p
     L.pe_state_bytes.argtypes = [P]
     L.pe_state_bytes.restype = U64
+    if hasattr(L, "pe_internal_plan"):  # (not part of the ABI: csrc/pe_handle.hpp)
+        L.pe_internal_plan.argtypes = [CP, I32, I32, ctypes.POINTER(PEPlanInfo)]
+        L.pe_internal_plan.restype = ctypes.c_int
     L.pe_last_error.argtypes = []
     L.pe_last_error.restype = ctypes.c_char_p
     D = ctypes.c_double
@@ -222,6 +235,14 @@ def check(rc, what):
         if rc == PE_ERR_NOROOM:
             raise ValueError(f"{what}: {msg}")
         raise PlantOSNativeError(f"{what} failed ({rc}): {msg}")
+
+
+def plan(cfg, n_envs, num_cus):
+    """pe_internal_plan: the kernel, reset paths and allocation sizes pe_create would choose for
+    `cfg` and `n_envs` on a device of `num_cus` CUs.  Needs no device; raises as pe_create does."""
+    info = PEPlanInfo()
+    check(lib().pe_internal_plan(ctypes.byref(cfg), int(n_envs), int(num_cus), ctypes.byref(info)), "pe_create")
+    return info
 
 
 def default_config(grid_size, num_plants, num_obstacles, lidar_range, lidar_channels):
