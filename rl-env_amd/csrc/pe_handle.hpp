@@ -65,5 +65,17 @@ struct pe_plan_info {
   uint64_t prefetch_bytes;  // the prefetched resets' allocation (0: none)
 };
 extern "C" int pe_internal_plan(const pe_config* c, int32_t n_envs, int32_t num_cus, pe_plan_info* out);
+// pe_internal_policy_plan (pe_policy.hip): what pe_policy_create (lstms null) or
+// pe_policy_create_lstm would decide for obs rows of D values, before they touch a device
+// (pe_policy_plan.hpp) -- no HIP call.  On rejection their error code, with pe_last_error() set.
+struct pe_policy_plan_info {
+  int32_t env_tile;        // pe_policy_env_tile()
+  uint64_t lds_bytes;      // a forward workgroup's dynamic LDS
+  uint64_t packed_floats;  // the packed weights
+  uint64_t state_floats;   // one (tower, h or c) LSTM state image; 0: feed-forward
+};
+extern "C" int pe_internal_policy_plan(int32_t D, int32_t n_envs, int32_t num_cus, int32_t n_towers,
+                                       const pe_policy_lstm* lstms, const pe_policy_tower* shapes, int32_t activation,
+                                       int32_t env_tile, pe_policy_plan_info* out);
 // pe_internal_render_free (pe_render.hip): frees the handle's render tables (pe_destroy).
 extern "C" void pe_internal_render_free(pe_handle* h);

@@ -34,6 +34,7 @@
 #include "../../include/plantos_batch.h"
 #include "pe_device.hpp"
 #include "pe_handle.hpp"
+#include "pe_host.hpp"
 
 using namespace pe;
 
@@ -858,34 +859,11 @@ __global__ void pe_mcts_seed_kernel(uint32_t* rng, int n, const uint32_t* seeds,
 }
 
 // ---------------------------------------------------------------- host side
-int fail(int code, const std::string& msg) { return pe_internal_set_error(code, msg.c_str()); }
-
-int hip_fail(hipError_t e, const char* what) {
-  return fail(PE_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 #define MC_HIP(call)                                   \
   do {                                                 \
     hipError_t _e = (call);                            \
     if (_e != hipSuccess) return hip_fail(_e, #call);  \
   } while (0)
-
-struct DevBind {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DevBind(int dev) {
-    (void)hipGetLastError();  // drop a stale error of an earlier call (launch checks below)
-    int cur = -1;
-    err = hipGetDevice(&cur);
-    if (err == hipSuccess && cur != dev) {
-      err = hipSetDevice(dev);
-      if (err == hipSuccess) prev = cur;
-    }
-  }
-  ~DevBind() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 // numpy (key, pos) -> device form (host; see the file comment)
 void np_to_device(const uint32_t* key, int pos, uint32_t* out) {
@@ -947,8 +925,8 @@ int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t 
   *out = nullptr;
   if (n_simulations < 0 || n_simulations > 65534) return fail(PE_ERR_ARG, "n_simulations must be in [0, 65534]");
   if (max_depth < 0 || max_depth > (1 << 20)) return fail(PE_ERR_ARG, "max_depth must be in [0, 2^20]");
-  DevBind db(h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(h->device);
+  if (dg.rc) return dg.rc;
   const size_t n = (size_t)h->n, GG = (size_t)h->g.GG;
   auto al = [](size_t v) { return (v + 255) / 256 * 256; };
   const size_t ggp = (GG + 15) / 16 * 16;
@@ -999,7 +977,7 @@ int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t 
 
 int pe_mcts_destroy(pe_mcts* m) {
   if (!m) return PE_OK;
-  DevBind db(m->h->device);
+  DeviceGuard dg(m->h->device);
   hipError_t e = hipFree(m->mem);
   delete m;
   return e == hipSuccess ? PE_OK : hip_fail(e, "hipFree");
@@ -1007,8 +985,8 @@ int pe_mcts_destroy(pe_mcts* m) {
 
 int pe_mcts_seed(pe_mcts* m, const uint32_t* seeds, uint32_t base_seed, void* stream) {
   if (!m) return fail(PE_ERR_ARG, "null handle");
-  DevBind db(m->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(m->h->device);
+  if (dg.rc) return dg.rc;
   const int n = m->h->n;
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint32_t* dseeds = nullptr;
@@ -1038,8 +1016,8 @@ int pe_mcts_set_rng(pe_mcts* m, const uint32_t* key, const int32_t* pos) {
     if (pos[e] < 0 || pos[e] > kMtN) return fail(PE_ERR_ARG, "pos must be in [0, 624]");
     np_to_device(key + (size_t)e * kMtN, pos[e], dev.data() + (size_t)e * kRngStride);
   }
-  DevBind db(m->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(m->h->device);
+  if (dg.rc) return dg.rc;
   MC_HIP(hipDeviceSynchronize());
   MC_HIP(hipMemcpy(m->rng, dev.data(), dev.size() * 4, hipMemcpyHostToDevice));
   return PE_OK;
@@ -1049,8 +1027,8 @@ int pe_mcts_get_rng(pe_mcts* m, uint32_t* key, int32_t* pos) {
   if (!m || !key || !pos) return fail(PE_ERR_ARG, "null argument");
   const int n = m->h->n;
   std::vector<uint32_t> dev((size_t)n * kRngStride);
-  DevBind db(m->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(m->h->device);
+  if (dg.rc) return dg.rc;
   MC_HIP(hipDeviceSynchronize());
   MC_HIP(hipMemcpy(dev.data(), m->rng, dev.size() * 4, hipMemcpyDeviceToHost));
   for (int e = 0; e < n; ++e) device_to_np(dev.data() + (size_t)e * kRngStride, key + (size_t)e * kMtN, pos + e);
@@ -1061,8 +1039,8 @@ int pe_mcts_search(pe_mcts* m, const uint8_t* mask, int32_t* actions, int32_t* r
                    double* root_value, void* stream) {
   if (!m || !actions) return fail(PE_ERR_ARG, "null argument");
   pe_handle* h = m->h;
-  DevBind db(h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(h->device);
+  if (dg.rc) return dg.rc;
   MctsArgs a;
   std::memset(&a, 0, sizeof(a));
   a.st = h->st;

@@ -24,8 +24,6 @@
 //      where asked for, the head outputs.
 // Activations never leave LDS / registers.  Nothing past row n - 1 of obs or of an
 // output is read or written.
-#include <algorithm>
-#include <new>
 #include <string>
 
 #include "pe_policy_impl.hpp"
@@ -115,7 +113,8 @@ __global__ __launch_bounds__(kThreads) void pe_policy_value_kernel(FwdArgs a, Va
 }
 
 // ---------------------------------------------------------------- host side
-size_t lds_bytes(int E, int Kp0, int HB) { return sizeof(float) * ((size_t)256 + (size_t)E * (kHeadRows + Kp0 + 2 * HB)); }
+const TileKernel kForward(pe_policy_forward_kernel<1>, pe_policy_forward_kernel<2>);
+const TileKernel kValue(pe_policy_value_kernel<1>, pe_policy_value_kernel<2>);
 
 // What every launch of p reads; the sampler and output fields are left zero.
 FwdArgs fwd_args(const pe_policy* p, const void* obs, int32_t obs_is_codes) {
@@ -141,77 +140,32 @@ FwdArgs fwd_args(const pe_policy* p, const void* obs, int32_t obs_is_codes) {
 
 extern "C" {
 
+int pe_internal_policy_plan(int32_t D, int32_t n_envs, int32_t num_cus, int32_t n_towers, const pe_policy_lstm* lstms,
+                            const pe_policy_tower* shapes, int32_t activation, int32_t env_tile,
+                            pe_policy_plan_info* out) {
+  if (!out) return fail(PE_ERR_ARG, "null argument");
+  PolicyPlan plan;
+  if (const int rc = make_policy_plan(D, n_envs, num_cus, n_towers, lstms, shapes, activation, env_tile, lstms != nullptr,
+                                      &plan))
+    return rc;
+  *out = {plan.env_tile, (uint64_t)plan.lds, (uint64_t)plan.n_packed, (uint64_t)plan.n_state};
+  return PE_OK;
+}
+
 int pe_policy_create(pe_handle* h, int32_t n_towers, const pe_policy_tower* shapes, int32_t activation,
                      int32_t env_tile, pe_policy** out) {
   if (!h || !out) return fail(PE_ERR_ARG, "null argument");
-  if (const int rc = pe_internal_policy_check(n_towers, shapes, activation, 0)) return rc;
-  if (env_tile != 0 && env_tile != 32 && env_tile != 64) return fail(PE_ERR_ARG, "env_tile must be 0, 32 or 64");
-  pe_policy* p = new (std::nothrow) pe_policy();
-  if (!p) return fail(PE_ERR_NOMEM, "host allocation failed");
-  p->h = h;
-  p->n_towers = n_towers;
-  p->act = activation;
-  p->D = h->g.D;
-  p->SD = p->D | 1;
-  p->Kp0 = (p->D + 7) & ~7;
-  int hmax = 0;
-  const size_t off = layout_towers(p, n_towers, shapes, p->D, 0, &hmax);
-  p->n_packed = off;
-  p->HB = std::max(hmax, p->SD);
-  const bool fits64 = lds_bytes(64, p->Kp0, p->HB) <= (size_t)kMaxLds;
-  const bool fits32 = lds_bytes(32, p->Kp0, p->HB) <= (size_t)kMaxLds;
-  // the library's choice: 64 envs per workgroup once that still gives every CU a workgroup
-  // (each workgroup streams the whole net), else 32
-  if (env_tile == 0) env_tile = (fits64 && (int64_t)h->n >= 64 * (int64_t)std::max(h->num_cus, 1)) ? 64 : 32;
-  if (!(env_tile == 64 ? fits64 : fits32)) {
-    delete p;
-    return fail(PE_ERR_ARG, "the env tile's activations do not fit 160 KiB of LDS (obs length / layer widths / env_tile)");
-  }
-  p->env_tile = env_tile;
-  p->lds = lds_bytes(env_tile, p->Kp0, p->HB);
-  DevBind db(h->device);
-  if (db.err != hipSuccess) {
-    delete p;
-    return hip_fail(db.err, "hipSetDevice");
-  }
-  const size_t bytes = (p->n_packed + 256) * sizeof(float);
-  hipError_t e = hipMalloc(&p->mem, bytes);
-  if (e != hipSuccess) {
-    delete p;
-    return fail(PE_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  float table[256];
-  pe_obs_code_table(h, table);
-  e = hipMemset(p->mem, 0, bytes);
-  if (e == hipSuccess) e = hipMemcpy(p->mem + p->n_packed, table, sizeof(table), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = env_tile == 64 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_forward_kernel<2>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
-                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_forward_kernel<1>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
-  if (e == hipSuccess && n_towers == 2)
-    e = env_tile == 64 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_value_kernel<2>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
-                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_value_kernel<1>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
-  if (e != hipSuccess) {
-    (void)hipFree(p->mem);
-    delete p;
-    return hip_fail(e, "pe_policy_create");
-  }
-  *out = p;
-  return PE_OK;
+  PolicyPlan plan;
+  if (const int rc = make_policy_plan(h->g.D, h->n, h->num_cus, n_towers, nullptr, shapes, activation, env_tile, false,
+                                      &plan))
+    return rc;
+  return create_policy(h, plan, {kForward.of(plan), n_towers == 2 ? kValue.of(plan) : nullptr}, "pe_policy_create", out);
 }
 
 int pe_policy_destroy(pe_policy* p) {
   if (!p) return PE_OK;
-  DevBind db(p->h->device);
-  hipError_t e = hipFree(p->mem);
-  if (p->state) {
-    const hipError_t es = hipFree(p->state);
-    if (e == hipSuccess) e = es;
-  }
-  delete p;
+  DeviceGuard dg(p->h);
+  const hipError_t e = free_policy(p);
   return e == hipSuccess ? PE_OK : hip_fail(e, "hipFree");
 }
 
@@ -224,8 +178,8 @@ int pe_policy_load(pe_policy* p, const pe_policy_tower* towers, void* stream) {
   int nl = 0;
   uint32_t most = 0;
   if (const int rc = pack_towers(p, towers, &a, &nl, &most)) return rc;
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(p->h);
+  if (dg.rc) return dg.rc;
   hipLaunchKernelGGL(pe_policy_pack_kernel, dim3((most + 255) / 256, (unsigned)nl), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a);
   const hipError_t le = hipGetLastError();
@@ -234,12 +188,9 @@ int pe_policy_load(pe_policy* p, const pe_policy_tower* towers, void* stream) {
 
 int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32_t mode, uint64_t seed,
                       uint32_t t, int32_t* actions, float* head0, float* head1, void* stream) {
-  if (!p || !obs || !actions) return fail(PE_ERR_ARG, "null argument");
-  if (p->H) return fail(PE_ERR_ARG, "a recurrent policy runs with pe_policy_forward_lstm");
-  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
-  if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
-    return fail(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
-  if (head1 && p->n_towers < 2) return fail(PE_ERR_ARG, "head1 needs a second tower");
+  if (const int rc = check_forward(p, false, obs, actions, obs_is_codes, mode, head1,
+                                   "a recurrent policy runs with pe_policy_forward_lstm"))
+    return rc;
   FwdArgs a = fwd_args(p, obs, obs_is_codes);
   a.mode = mode;
   a.seed = seed;
@@ -247,61 +198,32 @@ int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32
   a.actions = actions;
   a.head0 = head0;
   a.head1 = head1;
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
-  const int E = p->env_tile;
-  const dim3 grid((unsigned)((a.n + E - 1) / E)), block(kThreads);
-  if (E == 64)
-    hipLaunchKernelGGL(pe_policy_forward_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
-  else
-    hipLaunchKernelGGL(pe_policy_forward_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
-  const hipError_t le = hipGetLastError();
-  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_forward");
+  return kForward.launch(p, a.n, stream, "pe_policy_forward", a);
 }
 
 int pe_policy_forward_rows(pe_policy* p, int32_t rows, const void* obs, int32_t obs_is_codes, int32_t* actions,
                            float* head0, float* head1, void* stream) {
-  if (!p || !obs || !actions) return fail(PE_ERR_ARG, "null argument");
-  if (p->H) return fail(PE_ERR_ARG, "pe_policy_forward_rows does not evaluate a recurrent policy");
+  if (const int rc = check_forward(p, false, obs, actions, obs_is_codes, PE_POLICY_ARGMAX, head1,
+                                   "pe_policy_forward_rows does not evaluate a recurrent policy"))
+    return rc;
   if (rows < 1) return fail(PE_ERR_ARG, "rows must be >= 1, got " + std::to_string(rows));
-  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
-  if (head1 && p->n_towers < 2) return fail(PE_ERR_ARG, "head1 needs a second tower");
   FwdArgs a = fwd_args(p, obs, obs_is_codes);
   a.n = rows;  // the kernel bounds its last tile, its loads and its stores by a.n
   a.mode = PE_POLICY_ARGMAX;
   a.actions = actions;
   a.head0 = head0;
   a.head1 = head1;
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
-  const int E = p->env_tile;
-  const dim3 grid((unsigned)(((int64_t)a.n + E - 1) / E)), block(kThreads);
-  if (E == 64)
-    hipLaunchKernelGGL(pe_policy_forward_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
-  else
-    hipLaunchKernelGGL(pe_policy_forward_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
-  const hipError_t le = hipGetLastError();
-  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_forward_rows");
+  return kForward.launch(p, rows, stream, "pe_policy_forward_rows", a);
 }
 
 int pe_policy_value(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* want, const uint8_t* unless,
                     float* values, void* stream) {
-  if (!p || !obs || !values) return fail(PE_ERR_ARG, "null argument");
-  if (p->H) return fail(PE_ERR_ARG, "a recurrent policy runs with pe_policy_value_lstm");
+  if (const int rc = check_forward(p, false, obs, values, obs_is_codes, PE_POLICY_ARGMAX, nullptr,
+                                   "a recurrent policy runs with pe_policy_value_lstm"))
+    return rc;
   if (p->n_towers < 2) return fail(PE_ERR_ARG, "values need a second tower");
-  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
   const FwdArgs a = fwd_args(p, obs, obs_is_codes);
-  const ValueSel s{want, unless, values};
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
-  const int E = p->env_tile;
-  const dim3 grid((unsigned)((a.n + E - 1) / E)), block(kThreads);
-  if (E == 64)
-    hipLaunchKernelGGL(pe_policy_value_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
-  else
-    hipLaunchKernelGGL(pe_policy_value_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
-  const hipError_t le = hipGetLastError();
-  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_value");
+  return kValue.launch(p, a.n, stream, "pe_policy_value", a, ValueSel{want, unless, values});
 }
 
 }  // extern "C"

@@ -1,35 +1,25 @@
 // pe_policy_impl.hpp -- what the two policy translation units share (pe_policy.hip: the
-// feed-forward policy; pe_policy_lstm.hip: the recurrent one): the pe_policy object, the
-// layer tables, the MFMA hidden layer, the weight packing kernel and the host helpers.
+// feed-forward policy; pe_policy_lstm.hip: the recurrent one): the pe_policy object, the MFMA
+// hidden layer, the weight packing kernel and the host side's one create, launch and argument
+// check.  What a policy is made of is decided in pe_policy_plan.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+#include <memory>
+#include <new>
 #include <string>
 
 #include "../../include/plantos_batch.h"
-#include "pe_handle.hpp"
+#include "pe_host.hpp"
 #include "pe_policy_math.hpp"
-
-extern "C" int pe_internal_policy_check(int32_t n_towers, const pe_policy_tower* tw, int32_t activation,
-                                        int with_ptrs);
-extern "C" int pe_internal_policy_lstm_check(int32_t n_towers, const pe_policy_lstm* ls, int with_ptrs);
+#include "pe_policy_plan.hpp"
 
 namespace pe_pol {
 
 constexpr int kThreads = 512, kWaves = kThreads / 64;
-constexpr int kMaxLds = 160 * 1024;
-constexpr int kHeadRows = 9;  // tower 0's <= 8 outputs + the value
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Layer {
-  int K, Kp, N;            // inputs, inputs padded to a multiple of 8 (hidden layers), outputs
-  uint32_t off_w, off_b;   // float offsets into the packed buffer
-};
-struct Tower {
-  int n_hidden, n_out;
-  Layer l[4];  // hidden layers, then the head
-};
 
 struct PackLayer {
   const float* w;
@@ -44,20 +34,11 @@ struct PackArgs {
 
 }  // namespace pe_pol
 
-struct pe_policy {
+// A policy is its plan (pe_policy_plan.hpp), the handle whose obs it reads and two allocations.
+struct pe_policy : pe_pol::PolicyPlan {
   pe_handle* h;
-  int n_towers, act, env_tile;
-  int D, SD, Kp0, HB;
-  pe_pol::Tower tw[2];
-  float* mem;        // packed weights, then the code table
-  size_t n_packed;   // floats
-  size_t lds;
-  // recurrent policies only (H = 0: feed-forward)
-  int H;                   // LSTM hidden size
-  uint32_t off_lw[2];      // packed gate weights of tower i: [unit tile][k group][gate][lane][4]
-  uint32_t off_lb[2];      // bias_ih + bias_hh of tower i: [4H]
-  float* state;            // [tower][h, c][env tile][H][env_tile]
-  size_t n_state;          // floats of one (tower, h or c) image: tiles * H * env_tile
+  float* mem;    // packed weights, then the code table
+  float* state;  // recurrent policies only: [tower][h, c][env tile][H][env_tile]
 };
 
 namespace {
@@ -231,59 +212,77 @@ __device__ __forceinline__ void store_values(const float* hd, bool sel, int64_t 
 }
 
 // ---------------------------------------------------------------- host side
-inline int fail(int code, const std::string& msg) { return pe_internal_set_error(code, msg.c_str()); }
-
-inline int hip_fail(hipError_t e, const char* what) {
-  return fail(PE_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-inline int check_obs_kind(const pe_policy* p, int32_t obs_is_codes) {
-  if (obs_is_codes != 0 && obs_is_codes != 1) return fail(PE_ERR_ARG, "obs_is_codes must be 0 or 1");
-  if (obs_is_codes && !p->h->obs_codes) return fail(PE_ERR_ARG, "obs_is_codes = 1 needs a handle created with obs_codes");
-  return PE_OK;
-}
-
-struct DevBind {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DevBind(int dev) {
-    (void)hipGetLastError();  // drop a stale error of an earlier call (launch checks below)
-    int cur = -1;
-    err = hipGetDevice(&cur);
-    if (err == hipSuccess && cur != dev) {
-      err = hipSetDevice(dev);
-      if (err == hipSuccess) prev = cur;
-    }
+// Frees p and what it owns (the policy's device bound); the first error.
+inline hipError_t free_policy(pe_policy* p) {
+  hipError_t e = hipFree(p->mem);
+  if (p->state) {
+    const hipError_t es = hipFree(p->state);
+    if (e == hipSuccess) e = es;
   }
-  ~DevBind() {
-    if (prev >= 0) (void)hipSetDevice(prev);
+  delete p;
+  return e;
+}
+struct PolicyDeleter {
+  void operator()(pe_policy* p) const { (void)free_policy(p); }
+};
+
+// The two instantiations of a forward kernel, for tiles of 32 and of 64 envs.
+template <class... A>
+struct TileKernel {
+  void (*k32)(A...);
+  void (*k64)(A...);
+  TileKernel(void (*a)(A...), void (*b)(A...)) : k32(a), k64(b) {}
+  const void* of(const PolicyPlan& p) const { return reinterpret_cast<const void*>(p.env_tile == 64 ? k64 : k32); }
+  // p's instantiation over `rows` obs rows on `stream`; PE_OK or the launch error, named `what`
+  int launch(const pe_policy* p, int64_t rows, void* stream, const char* what, const A&... args) const {
+    DeviceGuard dg(p->h);
+    if (dg.rc) return dg.rc;
+    const int E = p->env_tile;
+    hipLaunchKernelGGL(E == 64 ? k64 : k32, dim3((unsigned)((rows + E - 1) / E)), dim3(kThreads), p->lds,
+                       static_cast<hipStream_t>(stream), args...);
+    const hipError_t le = hipGetLastError();
+    return le == hipSuccess ? PE_OK : hip_fail(le, what);
   }
 };
 
-// Fills p's layer tables of `n_towers` towers whose first layer reads K0 inputs, packed from
-// float offset `off` on; returns the end offset and the widest hidden layer.
-inline size_t layout_towers(pe_policy* p, int n_towers, const pe_policy_tower* shapes, int K0, size_t off, int* hmax) {
-  *hmax = 0;
-  for (int i = 0; i < n_towers; ++i) {
-    Tower& t = p->tw[i];
-    t.n_hidden = shapes[i].n_hidden;
-    t.n_out = shapes[i].n_out;
-    int K = K0;
-    for (int l = 0; l <= t.n_hidden; ++l) {
-      Layer& L = t.l[l];
-      const bool head = l == t.n_hidden;
-      L.K = K;
-      L.Kp = head ? K : (K + 7) & ~7;
-      L.N = head ? t.n_out : shapes[i].hidden[l];
-      L.off_w = (uint32_t)off;
-      off += (size_t)L.N * L.Kp;
-      L.off_b = (uint32_t)off;
-      off += ((size_t)L.N + 3) & ~(size_t)3;  // every offset stays a multiple of 16 B
-      if (!head) *hmax = *hmax > L.N ? *hmax : L.N;
-      K = L.N;
-    }
-  }
-  return off;
+// The policy of `plan` over h's envs: the allocations zeroed, the code table uploaded and the
+// dynamic-LDS limit of `kernels` (TileKernel::of; null entries skipped) raised to the plan's.
+// Every exit before the last frees what was made.
+inline int create_policy(pe_handle* h, const PolicyPlan& plan, std::initializer_list<const void*> kernels,
+                         const char* what, pe_policy** out) {
+  DeviceGuard dg(h);
+  if (dg.rc) return dg.rc;
+  std::unique_ptr<pe_policy, PolicyDeleter> p(new (std::nothrow) pe_policy{plan, h, nullptr, nullptr});
+  if (!p) return fail(PE_ERR_NOMEM, "host allocation failed");
+  const size_t bytes = (p->n_packed + 256) * sizeof(float);
+  const size_t state_bytes = (size_t)2 * p->n_towers * p->n_state * sizeof(float);
+  hipError_t e = hipMalloc(&p->mem, bytes);
+  if (e == hipSuccess && state_bytes) e = hipMalloc(&p->state, state_bytes);
+  if (e != hipSuccess) return fail(PE_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  float table[256];
+  pe_obs_code_table(h, table);
+  e = hipMemset(p->mem, 0, bytes);
+  if (e == hipSuccess && state_bytes) e = hipMemset(p->state, 0, state_bytes);
+  if (e == hipSuccess) e = hipMemcpy(p->mem + p->n_packed, table, sizeof(table), hipMemcpyHostToDevice);
+  for (const void* k : kernels)
+    if (e == hipSuccess && k) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
+  if (e != hipSuccess) return hip_fail(e, what);
+  *out = p.release();
+  return PE_OK;
+}
+
+// The argument checks the forwards share.  wrong_kind: the error of a policy of the other kind
+// (want_recurrent says which this entry point evaluates); out: the output that must be there.
+inline int check_forward(const pe_policy* p, bool want_recurrent, const void* obs, const void* out,
+                         int32_t obs_is_codes, int32_t mode, const float* head1, const char* wrong_kind) {
+  if (!p || !obs || !out) return fail(PE_ERR_ARG, "null argument");
+  if ((p->H != 0) != want_recurrent) return fail(PE_ERR_ARG, wrong_kind);
+  if (obs_is_codes != 0 && obs_is_codes != 1) return fail(PE_ERR_ARG, "obs_is_codes must be 0 or 1");
+  if (obs_is_codes && !p->h->obs_codes) return fail(PE_ERR_ARG, "obs_is_codes = 1 needs a handle created with obs_codes");
+  if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
+    return fail(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
+  if (head1 && p->n_towers < 2) return fail(PE_ERR_ARG, "head1 needs a second tower");
+  return PE_OK;
 }
 
 // The pack arguments of p's MLP layers from the caller's device tensors; PE_OK or PE_ERR_ARG.

@@ -21,7 +21,6 @@
 // The state is kept in the kernel's own order, [tower][h, c][env tile][unit][env in tile]:
 // the tile's image is contiguous, and the lanes' c / h accesses are 128-B rows.
 #include <algorithm>
-#include <new>
 #include <string>
 
 #include "pe_policy_impl.hpp"
@@ -277,9 +276,8 @@ __global__ __launch_bounds__(256) void pe_policy_lstm_state_kernel(float* img, f
     img[s] = user[i];
 }
 
-size_t lstm_lds_bytes(int E, int Kp0, int HB) {
-  return sizeof(float) * ((size_t)256 + (size_t)E * (kHeadRows + Kp0 + 2 * HB));
-}
+const TileKernel kForward(pe_policy_lstm_forward_kernel<1>, pe_policy_lstm_forward_kernel<2>);
+const TileKernel kValue(pe_policy_lstm_value_kernel<1>, pe_policy_lstm_value_kernel<2>);
 
 // What every launch of p reads; the sampler and output fields are left zero.
 LstmArgs lstm_args(const pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* start_a,
@@ -315,8 +313,8 @@ int state_copy(pe_policy* p, int tower, float* h, float* c, void* stream, int to
   if (!p) return fail(PE_ERR_ARG, "null policy");
   if (!p->H) return fail(PE_ERR_ARG, "not a recurrent policy");
   if (tower < 0 || tower >= p->n_towers) return fail(PE_ERR_ARG, "no such tower");
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(p->h);
+  if (dg.rc) return dg.rc;
   const int n = p->h->n;
   const unsigned blocks = (unsigned)(((int64_t)n * p->H + 255) / 256);
   float* user[2] = {h, c};
@@ -335,79 +333,12 @@ extern "C" {
 int pe_policy_create_lstm(pe_handle* h, int32_t n_towers, const pe_policy_lstm* lstms, const pe_policy_tower* shapes,
                           int32_t activation, int32_t env_tile, pe_policy** out) {
   if (!h || !out) return fail(PE_ERR_ARG, "null argument");
-  if (const int rc = pe_internal_policy_check(n_towers, shapes, activation, 0)) return rc;
-  if (const int rc = pe_internal_policy_lstm_check(n_towers, lstms, 0)) return rc;
-  if (env_tile != 0 && env_tile != 32 && env_tile != 64) return fail(PE_ERR_ARG, "env_tile must be 0, 32 or 64");
-  pe_policy* p = new (std::nothrow) pe_policy();
-  if (!p) return fail(PE_ERR_NOMEM, "host allocation failed");
-  p->h = h;
-  p->n_towers = n_towers;
-  p->act = activation;
-  p->D = h->g.D;
-  p->SD = p->D | 1;
-  p->Kp0 = (p->D + 7) & ~7;
-  p->H = lstms[0].hidden;
-  size_t off = 0;
-  for (int i = 0; i < n_towers; ++i) {
-    p->off_lw[i] = (uint32_t)off;
-    off += (size_t)4 * p->H * (p->Kp0 + p->H);
-    p->off_lb[i] = (uint32_t)off;
-    off += (size_t)4 * p->H;
-  }
-  int hmax = 0;
-  p->n_packed = layout_towers(p, n_towers, shapes, p->H, off, &hmax);
-  p->HB = std::max(std::max(hmax, p->H), p->SD);
-  const bool fits64 = lstm_lds_bytes(64, p->Kp0, p->HB) <= (size_t)kMaxLds;
-  const bool fits32 = lstm_lds_bytes(32, p->Kp0, p->HB) <= (size_t)kMaxLds;
-  if (env_tile == 0) env_tile = (fits64 && (int64_t)h->n >= 64 * (int64_t)std::max(h->num_cus, 1)) ? 64 : 32;
-  if (!(env_tile == 64 ? fits64 : fits32)) {
-    delete p;
-    return fail(PE_ERR_ARG, "the env tile's obs, h and activation images do not fit 160 KiB of LDS "
-                            "(obs length / lstm hidden size / layer widths / env_tile; a hidden size of 512 needs env_tile 32)");
-  }
-  p->env_tile = env_tile;
-  p->lds = lstm_lds_bytes(env_tile, p->Kp0, p->HB);
-  const size_t tiles = ((size_t)h->n + env_tile - 1) / env_tile;
-  p->n_state = tiles * p->H * env_tile;
-  DevBind db(h->device);
-  if (db.err != hipSuccess) {
-    delete p;
-    return hip_fail(db.err, "hipSetDevice");
-  }
-  const size_t bytes = (p->n_packed + 256) * sizeof(float);
-  const size_t state_bytes = (size_t)2 * n_towers * p->n_state * sizeof(float);
-  hipError_t e = hipMalloc(&p->mem, bytes);
-  if (e == hipSuccess) {
-    e = hipMalloc(&p->state, state_bytes);
-    if (e != hipSuccess) (void)hipFree(p->mem);
-  }
-  if (e != hipSuccess) {
-    delete p;
-    return fail(PE_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  float table[256];
-  pe_obs_code_table(h, table);
-  e = hipMemset(p->mem, 0, bytes);
-  if (e == hipSuccess) e = hipMemset(p->state, 0, state_bytes);
-  if (e == hipSuccess) e = hipMemcpy(p->mem + p->n_packed, table, sizeof(table), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = env_tile == 64 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_lstm_forward_kernel<2>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
-                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_lstm_forward_kernel<1>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
-  if (e == hipSuccess && n_towers == 2)
-    e = env_tile == 64 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_lstm_value_kernel<2>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds)
-                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&pe_policy_lstm_value_kernel<1>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
-  if (e != hipSuccess) {
-    (void)hipFree(p->mem);
-    (void)hipFree(p->state);
-    delete p;
-    return hip_fail(e, "pe_policy_create_lstm");
-  }
-  *out = p;
-  return PE_OK;
+  PolicyPlan plan;
+  if (const int rc = make_policy_plan(h->g.D, h->n, h->num_cus, n_towers, lstms, shapes, activation, env_tile, true,
+                                      &plan))
+    return rc;
+  return create_policy(h, plan, {kForward.of(plan), n_towers == 2 ? kValue.of(plan) : nullptr}, "pe_policy_create_lstm",
+                       out);
 }
 
 int pe_policy_load_lstm(pe_policy* p, const pe_policy_lstm* lstms, const pe_policy_tower* towers, void* stream) {
@@ -433,8 +364,8 @@ int pe_policy_load_lstm(pe_policy* p, const pe_policy_lstm* lstms, const pe_poli
   la.D = p->D;
   la.Kp0 = p->Kp0;
   la.H = p->H;
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(p->h);
+  if (dg.rc) return dg.rc;
   const uint32_t n_l = (uint32_t)(4 * p->H * (p->Kp0 + p->H) + 4 * p->H);
   hipLaunchKernelGGL(pe_policy_lstm_pack_kernel, dim3((n_l + 255) / 256, (unsigned)p->n_towers), dim3(256), 0,
                      static_cast<hipStream_t>(stream), la);
@@ -447,12 +378,9 @@ int pe_policy_load_lstm(pe_policy* p, const pe_policy_lstm* lstms, const pe_poli
 int pe_policy_forward_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* start_a,
                            const uint8_t* start_b, int32_t mode, uint64_t seed, uint32_t t, int32_t* actions,
                            float* head0, float* head1, void* stream) {
-  if (!p || !obs || !actions) return fail(PE_ERR_ARG, "null argument");
-  if (!p->H) return fail(PE_ERR_ARG, "a feed-forward policy runs with pe_policy_forward");
-  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
-  if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
-    return fail(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
-  if (head1 && p->n_towers < 2) return fail(PE_ERR_ARG, "head1 needs a second tower");
+  if (const int rc = check_forward(p, true, obs, actions, obs_is_codes, mode, head1,
+                                   "a feed-forward policy runs with pe_policy_forward"))
+    return rc;
   LstmArgs a = lstm_args(p, obs, obs_is_codes, start_a, start_b);
   a.mode = mode;
   a.seed = seed;
@@ -460,44 +388,25 @@ int pe_policy_forward_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, 
   a.actions = actions;
   a.head0 = head0;
   a.head1 = head1;
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
-  const int E = p->env_tile;
-  const dim3 grid((unsigned)((a.n + E - 1) / E)), block(kThreads);
-  if (E == 64)
-    hipLaunchKernelGGL(pe_policy_lstm_forward_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
-  else
-    hipLaunchKernelGGL(pe_policy_lstm_forward_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a);
-  const hipError_t le = hipGetLastError();
-  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_forward_lstm");
+  return kForward.launch(p, a.n, stream, "pe_policy_forward_lstm", a);
 }
 
 int pe_policy_value_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* start_a,
                          const uint8_t* start_b, const uint8_t* want, const uint8_t* unless, float* values,
                          void* stream) {
-  if (!p || !obs || !values) return fail(PE_ERR_ARG, "null argument");
-  if (!p->H) return fail(PE_ERR_ARG, "a feed-forward policy runs with pe_policy_value");
+  if (const int rc = check_forward(p, true, obs, values, obs_is_codes, PE_POLICY_ARGMAX, nullptr,
+                                   "a feed-forward policy runs with pe_policy_value"))
+    return rc;
   if (p->n_towers < 2) return fail(PE_ERR_ARG, "values need a second tower");
-  if (const int rc = check_obs_kind(p, obs_is_codes)) return rc;
   const LstmArgs a = lstm_args(p, obs, obs_is_codes, start_a, start_b);
-  const ValueSel s{want, unless, values};
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
-  const int E = p->env_tile;
-  const dim3 grid((unsigned)((a.n + E - 1) / E)), block(kThreads);
-  if (E == 64)
-    hipLaunchKernelGGL(pe_policy_lstm_value_kernel<2>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
-  else
-    hipLaunchKernelGGL(pe_policy_lstm_value_kernel<1>, grid, block, p->lds, static_cast<hipStream_t>(stream), a, s);
-  const hipError_t le = hipGetLastError();
-  return le == hipSuccess ? PE_OK : hip_fail(le, "pe_policy_value_lstm");
+  return kValue.launch(p, a.n, stream, "pe_policy_value_lstm", a, ValueSel{want, unless, values});
 }
 
 int pe_policy_lstm_reset_state(pe_policy* p, void* stream) {
   if (!p) return fail(PE_ERR_ARG, "null policy");
   if (!p->H) return fail(PE_ERR_ARG, "not a recurrent policy");
-  DevBind db(p->h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(p->h);
+  if (dg.rc) return dg.rc;
   const hipError_t e = hipMemsetAsync(p->state, 0, (size_t)2 * p->n_towers * p->n_state * sizeof(float),
                                       static_cast<hipStream_t>(stream));
   return e == hipSuccess ? PE_OK : hip_fail(e, "pe_policy_lstm_reset_state");

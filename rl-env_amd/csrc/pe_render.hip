@@ -60,6 +60,7 @@
 #include "../../include/plantos_batch.h"
 #include "pe_device.hpp"
 #include "pe_handle.hpp"
+#include "pe_host.hpp"
 
 namespace {
 using namespace pe;
@@ -270,29 +271,6 @@ __global__ __launch_bounds__(kThreads) void pe_render_kernel(RenderArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-int fail(int code, const std::string& msg) { return pe_internal_set_error(code, msg.c_str()); }
-
-int hip_fail(hipError_t e, const char* what) {
-  return fail(PE_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-struct DevBind {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DevBind(int dev) {
-    (void)hipGetLastError();  // drop a stale error of an earlier call (launch check below)
-    int cur = -1;
-    err = hipGetDevice(&cur);
-    if (err == hipSuccess && cur != dev) {
-      err = hipSetDevice(dev);
-      if (err == hipSuccess) prev = cur;
-    }
-  }
-  ~DevBind() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 // The per-cell_size device tables of one handle.  A table is uploaded once, before its
 // first launch, into memory of its own and never written again, so an earlier launch
 // still running on the stream reads its table undisturbed; all are freed by pe_destroy.
@@ -365,8 +343,8 @@ int pe_render(pe_handle* h, int32_t k, const int32_t* env_index, int32_t cell_si
   a.by_upr = make_div((uint32_t)(a.WP >> 4));
   a.by_slots = make_div((uint32_t)((3 * W + 15) / 16 + 1));
   if ((int64_t)k * a.nb > (1 << 22)) return fail(PE_ERR_ARG, "too many frames for one call");
-  DevBind db(h->device);
-  if (db.err != hipSuccess) return hip_fail(db.err, "hipSetDevice");
+  DeviceGuard dg(h->device);
+  if (dg.rc) return dg.rc;
 
   RenderCache* rc = static_cast<RenderCache*>(h->render_cache);
   if (!rc) {

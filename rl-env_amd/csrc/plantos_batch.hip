@@ -2871,55 +2871,17 @@ __global__ __launch_bounds__(256) void pe_expand_codes_kernel(const Tables* tab,
 }
 
 // ====================================================================== host side
-#include "pe_handle.hpp"
+#include "pe_host.hpp"  // fail / hip_fail / DeviceGuard
 
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-  return fail(PE_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 #define PE_HIP(call)                                   \
   do {                                                 \
     hipError_t _e = (call);                            \
     if (_e != hipSuccess) return hip_fail(_e, #call);  \
   } while (0)
-
-// Binds the handle's device for one API call and restores the caller's device
-// afterwards (the library never leaves the calling thread on another device).
-struct DeviceGuard {
-  int prev = -1;
-  int rc = PE_OK;
-  explicit DeviceGuard(const pe_handle* h) : DeviceGuard(h->device) {}
-  explicit DeviceGuard(int device) {
-    // hipGetLastError() reports the last failed runtime call of this thread,
-    // whoever made it (torch probes, the caller's own calls): drop such a stale
-    // error so the launch checks below see only this call's launches.
-    (void)hipGetLastError();
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) {
-      rc = hip_fail(e, "hipGetDevice");
-      prev = -1;
-      return;
-    }
-    if (prev != device) {
-      e = hipSetDevice(device);
-      if (e != hipSuccess) rc = hip_fail(e, "hipSetDevice");
-    } else {
-      prev = -1;
-    }
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 StepArgs base_args(const pe_handle* h) {
   StepArgs a;
@@ -3099,7 +3061,10 @@ int32_t pe_obs_dim(const pe_config* c) { return c->lidar_channels * 5 + 2 + 25; 
 
 const char* pe_last_error(void) { return g_err.c_str(); }
 
-int pe_internal_set_error(int code, const char* msg) { return fail(code, msg); }
+int pe_internal_set_error(int code, const char* msg) {
+  g_err = msg;
+  return code;
+}
 
 int pe_internal_plan(const pe_config* c, int32_t n_envs, int32_t num_cus, pe_plan_info* out) {
   if (!c || !out) return fail(PE_ERR_ARG, "null argument");

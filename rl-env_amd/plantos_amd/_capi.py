@@ -97,6 +97,12 @@ class PEPlanInfo(ctypes.Structure):
     ]
 
 
+class PEPolicyPlanInfo(ctypes.Structure):
+    """pe_policy_plan_info (csrc/pe_handle.hpp): what pe_policy_create[_lstm] would decide, without a device."""
+    _fields_ = [("env_tile", ctypes.c_int32), ("lds_bytes", ctypes.c_uint64), ("packed_floats", ctypes.c_uint64),
+                ("state_floats", ctypes.c_uint64)]
+
+
 class PlantOSNativeError(RuntimeError):
     pass
 
@@ -148,6 +154,10 @@ def lib():
     if hasattr(L, "pe_internal_plan"):  # (not part of the ABI: csrc/pe_handle.hpp)
         L.pe_internal_plan.argtypes = [CP, I32, I32, ctypes.POINTER(PEPlanInfo)]
         L.pe_internal_plan.restype = ctypes.c_int
+    if hasattr(L, "pe_internal_policy_plan"):  # (not part of the ABI: csrc/pe_handle.hpp)
+        L.pe_internal_policy_plan.argtypes = [I32, I32, I32, I32, ctypes.POINTER(PEPolicyLstm),
+                                              ctypes.POINTER(PEPolicyTower), I32, I32, ctypes.POINTER(PEPolicyPlanInfo)]
+        L.pe_internal_policy_plan.restype = ctypes.c_int
     L.pe_last_error.argtypes = []
     L.pe_last_error.restype = ctypes.c_char_p
     D = ctypes.c_double
@@ -242,6 +252,18 @@ def plan(cfg, n_envs, num_cus):
     `cfg` and `n_envs` on a device of `num_cus` CUs.  Needs no device; raises as pe_create does."""
     info = PEPlanInfo()
     check(lib().pe_internal_plan(ctypes.byref(cfg), int(n_envs), int(num_cus), ctypes.byref(info)), "pe_create")
+    return info
+
+
+def policy_plan(obs_dim, n_envs, num_cus, lstms, shapes, activation, env_tile=0):
+    """pe_internal_policy_plan: the env tile, LDS and buffer sizes pe_policy_create (lstms None) or
+    pe_policy_create_lstm would choose for obs rows of `obs_dim` values, `n_envs` envs and a device of
+    `num_cus` CUs.  lstms / shapes: PEPolicyLstm / PEPolicyTower arrays.  Needs no device; raises as
+    the create call does."""
+    info = PEPolicyPlanInfo()
+    check(lib().pe_internal_policy_plan(int(obs_dim), int(n_envs), int(num_cus), len(shapes), lstms, shapes,
+                                        int(activation), int(env_tile), ctypes.byref(info)),
+          "pe_policy_create" if lstms is None else "pe_policy_create_lstm")
     return info
 
 

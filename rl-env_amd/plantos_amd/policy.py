@@ -184,54 +184,25 @@ def _np(x):
     return x if isinstance(x, np.ndarray) else x.detach().cpu().numpy()
 
 
-def _value_args(pol, obs, select, out):
-    """The checked arguments of Policy.value / RecurrentPolicy.value: (obs, codes, want pointer,
-    unless pointer, out).  ValueError as act's."""
-    torch, b = pol._torch, pol.batch
-    n, D = b.num_envs, b.obs_dim
-    if len(pol.towers) < 2:
-        raise ValueError("a one-tower policy has no values")
-    if obs is None:
-        obs = b.obs
-    if not (type(obs) is torch.Tensor and obs.is_cuda and obs.get_device() == b._dev_index
-            and obs.is_contiguous() and tuple(obs.shape) == (n, D)
-            and (obs.dtype is torch.float32 or obs.dtype is torch.uint8)):
-        raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape {(n, D)} on {b.device}")
-    codes = obs.dtype is torch.uint8
-    if codes and not b.obs_codes:
-        raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
-    if isinstance(select, (tuple, list)):
-        if len(select) != 2:
-            raise ValueError("select must be a tensor or a pair (want, unless) of tensors")
-        want, unless = select
-    else:
-        want, unless = select, None
-    ptrs = []
-    for name, x in (("select / want", want), ("unless", unless)):
-        if x is not None and not (type(x) is torch.Tensor and x.is_cuda and x.get_device() == b._dev_index
-                                  and x.is_contiguous() and tuple(x.shape) == (n,)
-                                  and (x.dtype is torch.uint8 or x.dtype is torch.bool)):
-            raise ValueError(f"{name} must be a contiguous uint8 or bool tensor of shape {(n,)} on {b.device}")
-        ptrs.append(None if x is None else x.data_ptr())
-    if out is None:
-        out = pol.values
-    if not (type(out) is torch.Tensor and out.dtype is torch.float32 and out.is_cuda
-            and out.get_device() == b._dev_index and out.is_contiguous() and tuple(out.shape) == (n,)):
-        raise ValueError(f"out must be a contiguous float32 tensor of shape {(n,)} on {b.device}")
-    return obs, codes, ptrs[0], ptrs[1], out
+_TENSOR = None  # torch.Tensor, once torch is in use (this module imports without it)
 
 
-class Policy:
-    """An MLP policy over the obs of a PlantOSBatch (or of a PlantOSVecEnv's batch).
+def _on_dev(x, batch, dtypes, shape):
+    """Whether x is a plain torch tensor on the batch's device, contiguous, of one of `dtypes` and
+    of `shape` (None: any shape)."""
+    global _TENSOR
+    if _TENSOR is None:
+        import torch
+        _TENSOR = torch.Tensor
+    return (type(x) is _TENSOR and x.is_cuda and x.get_device() == batch._dev_index and x.is_contiguous()
+            and x.dtype in dtypes and (shape is None or tuple(x.shape) == shape))
 
-    towers: [[h1, .., A], [h1, .., 1]] (pi and vf nets) or [[h1, .., A]] (a Q-network);
-    activation "tanh" or "relu"; seed keys the action sampler (deterministic=False);
-    env_tile (32 / 64, None = the library's choice) is the kernel's envs per workgroup: it
-    changes speed, never results.  Weights start at zero: `load` them.  Close the policy
-    before its batch."""
 
-    def __init__(self, batch_or_venv, towers=((256, 256, 5), (256, 256, 1)), activation="tanh", seed=0,
-                 env_tile=None):
+class _PolicyBase:
+    """What Policy and RecurrentPolicy share: construction around the subclass's `_create`, the
+    handle, and the argument checks of act / value."""
+
+    def __init__(self, batch_or_venv, towers, activation, seed, env_tile):
         import torch
         self._torch = torch
         self.batch = getattr(batch_or_venv, "batch", batch_or_venv)
@@ -243,10 +214,8 @@ class Policy:
         self.t = 0  # sampler step counter: act(deterministic=False) without t uses and advances it
         b = self.batch
         p = ctypes.c_void_p()
-        shapes = _tower_structs(self.towers)
         with torch.cuda.device(b.device):
-            C.check(C.lib().pe_policy_create(b.handle, len(self.towers), shapes, ACTIVATIONS[activation],
-                                             int(env_tile or 0), ctypes.byref(p)), "pe_policy_create")
+            self._create(int(env_tile or 0), ctypes.byref(p))
         self._p = p
         n, A, dev = b.num_envs, self.towers[0][-1], b.device
         self.actions = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -254,22 +223,17 @@ class Policy:
         self.values = torch.zeros(n, dtype=torch.float32, device=dev) if len(self.towers) == 2 else None
         self._loaded = None
 
-    @classmethod
-    def from_state_dict(cls, env, sd, activation=None, **kw):
-        """A Policy shaped and loaded from a Stable-Baselines3 state dict (parse_state_dict)."""
-        towers, act, tensors = parse_state_dict(sd, activation)
-        p = cls(env, towers, act, **kw)
-        p.load(tensors)
-        return p
-
     @property
     def env_tile(self):
         return int(C.lib().pe_policy_env_tile(self._handle()))
 
     def _handle(self):
         if not self._p:
-            raise ValueError("Policy is closed")
+            raise ValueError(f"{type(self).__name__} is closed")
         return self._p
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.batch._dev_index).cuda_stream
 
     def close(self):
         if getattr(self, "_p", None):
@@ -281,6 +245,100 @@ class Policy:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+    def _obs_arg(self, obs, any_rows=False):
+        """(obs, codes): the checked obs of a forward -- None reads the batch's own; [n, D], or with
+        any_rows any number >= 1 of rows."""
+        torch, b = self._torch, self.batch
+        n, D = b.num_envs, b.obs_dim
+        if obs is None and not any_rows:
+            obs = b.obs
+        if not (_on_dev(obs, b, (torch.float32, torch.uint8), None if any_rows else (n, D))
+                and (not any_rows or (obs.dim() == 2 and obs.shape[0] >= 1 and obs.shape[1] == D))):
+            shape = f"(rows >= 1, {D})" if any_rows else (n, D)
+            raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape {shape} on {b.device}")
+        codes = obs.dtype is torch.uint8
+        if codes and not b.obs_codes:
+            raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
+        return obs, codes
+
+    def _out_arg(self, out, rows):
+        """(actions, logits, values) of `rows` rows to write: `out`, or the policy's own tensors."""
+        torch, b = self._torch, self.batch
+        a, lg, v = out if out is not None else (self.actions, self.logits, self.values)
+        A = self.towers[0][-1]
+        for name, x, dt, shape in (("actions", a, torch.int32, (rows,)), ("logits", lg, torch.float32, (rows, A)),
+                                   ("values", v, torch.float32, (rows,))):
+            if x is None and name != "actions":
+                continue  # an output not asked for
+            if not _on_dev(x, b, (dt,), shape):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {b.device}")
+        if v is not None and len(self.towers) < 2:
+            raise ValueError("a one-tower policy has no values")
+        return a, lg, v
+
+    def _sampler_step(self, deterministic, t):
+        """(mode, step) of a forward; sampling without t uses and advances the policy's counter."""
+        if deterministic:
+            return C.PE_POLICY_ARGMAX, 0
+        if t is None:
+            t, self.t = self.t, self.t + 1
+        return C.PE_POLICY_SAMPLE, int(t) & 0xFFFFFFFF
+
+    def _flag_arg(self, x, name):
+        """The pointer of a per-env flag tensor (uint8 / bool [n]), or None."""
+        torch, b = self._torch, self.batch
+        if x is None:
+            return None
+        if not _on_dev(x, b, (torch.uint8, torch.bool), (b.num_envs,)):
+            raise ValueError(f"{name} must be a contiguous uint8 or bool tensor of shape {(b.num_envs,)} on {b.device}")
+        return x.data_ptr()
+
+    def _value_args(self, obs, select, out):
+        """The checked arguments of value(): (obs, codes, want pointer, unless pointer, out).
+        ValueError as act's."""
+        b = self.batch
+        if len(self.towers) < 2:
+            raise ValueError("a one-tower policy has no values")
+        obs, codes = self._obs_arg(obs)
+        if isinstance(select, (tuple, list)):
+            if len(select) != 2:
+                raise ValueError("select must be a tensor or a pair (want, unless) of tensors")
+            want, unless = select
+        else:
+            want, unless = select, None
+        want, unless = self._flag_arg(want, "select / want"), self._flag_arg(unless, "unless")
+        if out is None:
+            out = self.values
+        if not _on_dev(out, b, (self._torch.float32,), (b.num_envs,)):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {(b.num_envs,)} on {b.device}")
+        return obs, codes, want, unless, out
+
+
+class Policy(_PolicyBase):
+    """An MLP policy over the obs of a PlantOSBatch (or of a PlantOSVecEnv's batch).
+
+    towers: [[h1, .., A], [h1, .., 1]] (pi and vf nets) or [[h1, .., A]] (a Q-network);
+    activation "tanh" or "relu"; seed keys the action sampler (deterministic=False);
+    env_tile (32 / 64, None = the library's choice) is the kernel's envs per workgroup: it
+    changes speed, never results.  Weights start at zero: `load` them.  Close the policy
+    before its batch."""
+
+    def __init__(self, batch_or_venv, towers=((256, 256, 5), (256, 256, 1)), activation="tanh", seed=0,
+                 env_tile=None):
+        super().__init__(batch_or_venv, towers, activation, seed, env_tile)
+
+    def _create(self, env_tile, out):
+        C.check(C.lib().pe_policy_create(self.batch.handle, len(self.towers), _tower_structs(self.towers),
+                                         ACTIVATIONS[self.activation], env_tile, out), "pe_policy_create")
+
+    @classmethod
+    def from_state_dict(cls, env, sd, activation=None, **kw):
+        """A Policy shaped and loaded from a Stable-Baselines3 state dict (parse_state_dict)."""
+        towers, act, tensors = parse_state_dict(sd, activation)
+        p = cls(env, towers, act, **kw)
+        p.load(tensors)
+        return p
 
     def load(self, sd_or_tensors):
         """Repack new weights into the policy: one kernel on the current stream, ordered with
@@ -315,41 +373,12 @@ class Policy:
         the policy's counter, which then advances).  out: (actions, logits, values) tensors to
         write instead of the policy's own (values None for a one-tower policy).  One kernel on
         the current stream; no sync, no allocation: graph-capturable."""
-        torch = self._torch
-        b = self.batch
-        n, D = b.num_envs, b.obs_dim
-        if obs is None:
-            obs = b.obs
-        if not (type(obs) is torch.Tensor and obs.is_cuda and obs.get_device() == b._dev_index
-                and obs.is_contiguous() and tuple(obs.shape) == (n, D)
-                and (obs.dtype is torch.float32 or obs.dtype is torch.uint8)):
-            raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape {(n, D)} on {b.device}")
-        codes = obs.dtype is torch.uint8
-        if codes and not b.obs_codes:
-            raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
-        a, lg, v = out if out is not None else (self.actions, self.logits, self.values)
-        A = self.towers[0][-1]
-        for name, x, dt, shape in (("actions", a, torch.int32, (n,)), ("logits", lg, torch.float32, (n, A)),
-                                   ("values", v, torch.float32, (n,))):
-            if x is None and name != "actions":
-                continue  # an output not asked for
-            if not (type(x) is torch.Tensor and x.dtype is dt and x.is_cuda and x.get_device() == b._dev_index
-                    and x.is_contiguous() and tuple(x.shape) == shape):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {b.device}")
-        if v is not None and len(self.towers) < 2:
-            raise ValueError("a one-tower policy has no values")
-        if deterministic:
-            mode, step = C.PE_POLICY_ARGMAX, 0
-        else:
-            mode = C.PE_POLICY_SAMPLE
-            if t is None:
-                step, self.t = self.t, self.t + 1
-            else:
-                step = int(t)
-        rc = C.lib().pe_policy_forward(self._handle(), obs.data_ptr(), int(codes), mode, self.seed,
-                                       step & 0xFFFFFFFF, a.data_ptr(), lg.data_ptr() if lg is not None else None,
-                                       v.data_ptr() if v is not None else None,
-                                       torch.cuda.current_stream(b._dev_index).cuda_stream)
+        obs, codes = self._obs_arg(obs)
+        a, lg, v = self._out_arg(out, self.batch.num_envs)
+        mode, step = self._sampler_step(deterministic, t)
+        rc = C.lib().pe_policy_forward(self._handle(), obs.data_ptr(), int(codes), mode, self.seed, step, a.data_ptr(),
+                                       lg.data_ptr() if lg is not None else None,
+                                       v.data_ptr() if v is not None else None, self._stream())
         if rc:
             C.check(rc, "pe_policy_forward")
         return a, lg, v
@@ -363,35 +392,17 @@ class Policy:
         (logits / values may be None: not asked for); without it new tensors are allocated.
         One kernel on the current stream; no sync, and with `out` no allocation:
         graph-capturable."""
-        torch = self._torch
-        b = self.batch
-        D, A = b.obs_dim, self.towers[0][-1]
-        if not (type(obs) is torch.Tensor and obs.is_cuda and obs.get_device() == b._dev_index
-                and obs.is_contiguous() and obs.dim() == 2 and obs.shape[0] >= 1 and obs.shape[1] == D
-                and (obs.dtype is torch.float32 or obs.dtype is torch.uint8)):
-            raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape (rows >= 1, {D}) on {b.device}")
-        rows = int(obs.shape[0])
-        codes = obs.dtype is torch.uint8
-        if codes and not b.obs_codes:
-            raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
+        torch, b = self._torch, self.batch
+        obs, codes = self._obs_arg(obs, any_rows=True)
+        rows, A = int(obs.shape[0]), self.towers[0][-1]
         if out is None:
             out = (torch.empty(rows, dtype=torch.int32, device=b.device),
                    torch.empty((rows, A), dtype=torch.float32, device=b.device),
                    torch.empty(rows, dtype=torch.float32, device=b.device) if len(self.towers) == 2 else None)
-        a, lg, v = out
-        for name, x, dt, shape in (("actions", a, torch.int32, (rows,)), ("logits", lg, torch.float32, (rows, A)),
-                                   ("values", v, torch.float32, (rows,))):
-            if x is None and name != "actions":
-                continue  # an output not asked for
-            if not (type(x) is torch.Tensor and x.dtype is dt and x.is_cuda and x.get_device() == b._dev_index
-                    and x.is_contiguous() and tuple(x.shape) == shape):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {b.device}")
-        if v is not None and len(self.towers) < 2:
-            raise ValueError("a one-tower policy has no values")
+        a, lg, v = self._out_arg(out, rows)
         rc = C.lib().pe_policy_forward_rows(self._handle(), rows, obs.data_ptr(), int(codes), a.data_ptr(),
                                             lg.data_ptr() if lg is not None else None,
-                                            v.data_ptr() if v is not None else None,
-                                            torch.cuda.current_stream(b._dev_index).cuda_stream)
+                                            v.data_ptr() if v is not None else None, self._stream())
         if rc:
             C.check(rc, "pe_policy_forward_rows")
         return a, lg, v
@@ -407,9 +418,9 @@ class Policy:
         selected costs no work.  out: a float32 tensor [n] to write instead of the policy's
         own values.  ValueError for a one-tower policy.  One kernel on the current stream; no
         sync, no allocation: graph-capturable."""
-        obs, codes, want, unless, out = _value_args(self, obs, select, out)
+        obs, codes, want, unless, out = self._value_args(obs, select, out)
         rc = C.lib().pe_policy_value(self._handle(), obs.data_ptr(), int(codes), want, unless, out.data_ptr(),
-                                     self._torch.cuda.current_stream(self.batch._dev_index).cuda_stream)
+                                     self._stream())
         if rc:
             C.check(rc, "pe_policy_value")
         return out
@@ -568,7 +579,7 @@ def lstm_host_forward(hidden, towers, lstm_tensors, mlp_tensors, activation, obs
     return (actions, logits, values), [(hs[i], cs[i]) for i in range(nt)]
 
 
-class RecurrentPolicy:
+class RecurrentPolicy(_PolicyBase):
     """An LSTM policy (sb3_contrib MlpLstmPolicy, one LSTM layer per tower) over the obs of a
     PlantOSBatch (or of a PlantOSVecEnv's batch).
 
@@ -579,28 +590,14 @@ class RecurrentPolicy:
     the policy before its batch."""
 
     def __init__(self, batch_or_venv, hidden, towers, activation="tanh", seed=0, env_tile=None):
-        import torch
-        self._torch = torch
-        self.batch = getattr(batch_or_venv, "batch", batch_or_venv)
         self.hidden = check_lstm_hidden(hidden)
-        self.towers = check_towers(towers)
-        if activation not in ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
-        self.activation = activation
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.t = 0  # sampler step counter: act(deterministic=False) without t uses and advances it
-        b = self.batch
-        p = ctypes.c_void_p()
-        with torch.cuda.device(b.device):
-            C.check(C.lib().pe_policy_create_lstm(b.handle, len(self.towers), _lstm_structs(self.hidden, len(self.towers)),
-                                                  _tower_structs(self.towers), ACTIVATIONS[activation],
-                                                  int(env_tile or 0), ctypes.byref(p)), "pe_policy_create_lstm")
-        self._p = p
-        n, A, dev = b.num_envs, self.towers[0][-1], b.device
-        self.actions = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.logits = torch.zeros((n, A), dtype=torch.float32, device=dev)
-        self.values = torch.zeros(n, dtype=torch.float32, device=dev) if len(self.towers) == 2 else None
-        self._loaded = None
+        super().__init__(batch_or_venv, towers, activation, seed, env_tile)
+
+    def _create(self, env_tile, out):
+        nt = len(self.towers)
+        C.check(C.lib().pe_policy_create_lstm(self.batch.handle, nt, _lstm_structs(self.hidden, nt),
+                                              _tower_structs(self.towers), ACTIVATIONS[self.activation], env_tile, out),
+                "pe_policy_create_lstm")
 
     @classmethod
     def from_state_dict(cls, env, sd, activation=None, **kw):
@@ -609,29 +606,6 @@ class RecurrentPolicy:
         p = cls(env, hidden, towers, act, **kw)
         p.load((lstm, mlp))
         return p
-
-    @property
-    def env_tile(self):
-        return int(C.lib().pe_policy_env_tile(self._handle()))
-
-    def _handle(self):
-        if not self._p:
-            raise ValueError("RecurrentPolicy is closed")
-        return self._p
-
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.batch._dev_index).cuda_stream
-
-    def close(self):
-        if getattr(self, "_p", None):
-            C.check(C.lib().pe_policy_destroy(self._p), "pe_policy_destroy")
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def load(self, sd_or_tensors):
         """Repack new weights: kernels on the current stream, ordered with the forwards around
@@ -659,15 +633,6 @@ class RecurrentPolicy:
         self._loaded = (dl, dm)  # alive until the next load (the kernels read them on the stream)
         return self
 
-    def _flag(self, x, name):
-        torch, b = self._torch, self.batch
-        if x is None:
-            return None
-        if not (type(x) is torch.Tensor and x.is_cuda and x.get_device() == b._dev_index and x.is_contiguous()
-                and tuple(x.shape) == (b.num_envs,) and (x.dtype is torch.uint8 or x.dtype is torch.bool)):
-            raise ValueError(f"{name} must be a contiguous uint8 or bool tensor of shape {(b.num_envs,)} on {b.device}")
-        return x.data_ptr()
-
     def act(self, obs=None, episode_start=None, deterministic=True, t=None, out=None):
         """(actions i32 [n], logits f32 [n, A], values f32 [n] or None), device tensors; the
         LSTM state of every env advances by one step.
@@ -676,40 +641,12 @@ class RecurrentPolicy:
         [n], or a pair of them -- the step's (terminated, truncated) as they are; an env whose
         flag (either one) is non-zero reads a zero state in this step.  None: no env starts.
         One kernel on the current stream; no sync, no allocation: graph-capturable."""
-        torch = self._torch
-        b = self.batch
-        n, D = b.num_envs, b.obs_dim
-        if obs is None:
-            obs = b.obs
-        if not (type(obs) is torch.Tensor and obs.is_cuda and obs.get_device() == b._dev_index
-                and obs.is_contiguous() and tuple(obs.shape) == (n, D)
-                and (obs.dtype is torch.float32 or obs.dtype is torch.uint8)):
-            raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape {(n, D)} on {b.device}")
-        codes = obs.dtype is torch.uint8
-        if codes and not b.obs_codes:
-            raise ValueError("uint8 obs codes need a batch created with obs_codes=True")
+        obs, codes = self._obs_arg(obs)
         sa, sb = self._starts(episode_start)
-        a, lg, v = out if out is not None else (self.actions, self.logits, self.values)
-        A = self.towers[0][-1]
-        for name, x, dt, shape in (("actions", a, torch.int32, (n,)), ("logits", lg, torch.float32, (n, A)),
-                                   ("values", v, torch.float32, (n,))):
-            if x is None and name != "actions":
-                continue  # an output not asked for
-            if not (type(x) is torch.Tensor and x.dtype is dt and x.is_cuda and x.get_device() == b._dev_index
-                    and x.is_contiguous() and tuple(x.shape) == shape):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {b.device}")
-        if v is not None and len(self.towers) < 2:
-            raise ValueError("a one-tower policy has no values")
-        if deterministic:
-            mode, step = C.PE_POLICY_ARGMAX, 0
-        else:
-            mode = C.PE_POLICY_SAMPLE
-            if t is None:
-                step, self.t = self.t, self.t + 1
-            else:
-                step = int(t)
+        a, lg, v = self._out_arg(out, self.batch.num_envs)
+        mode, step = self._sampler_step(deterministic, t)
         rc = C.lib().pe_policy_forward_lstm(self._handle(), obs.data_ptr(), int(codes), sa, sb, mode, self.seed,
-                                            step & 0xFFFFFFFF, a.data_ptr(), lg.data_ptr() if lg is not None else None,
+                                            step, a.data_ptr(), lg.data_ptr() if lg is not None else None,
                                             v.data_ptr() if v is not None else None, self._stream())
         if rc:
             C.check(rc, "pe_policy_forward_lstm")
@@ -719,8 +656,9 @@ class RecurrentPolicy:
         if isinstance(episode_start, (tuple, list)):
             if len(episode_start) != 2:
                 raise ValueError("episode_start must be a tensor or a pair of tensors")
-            return self._flag(episode_start[0], "episode_start[0]"), self._flag(episode_start[1], "episode_start[1]")
-        return self._flag(episode_start, "episode_start"), None
+            return (self._flag_arg(episode_start[0], "episode_start[0]"),
+                    self._flag_arg(episode_start[1], "episode_start[1]"))
+        return self._flag_arg(episode_start, "episode_start"), None
 
     def value(self, obs=None, episode_start=None, select=None, out=None):
         """The values f32 [n] alone, from the LSTM state as it is: bit for bit what `act` would
@@ -731,7 +669,7 @@ class RecurrentPolicy:
         obs, episode_start: as `act`.  select, out: as Policy.value.  ValueError for an
         actor-only policy.  One kernel on the current stream; no sync, no allocation:
         graph-capturable."""
-        obs, codes, want, unless, out = _value_args(self, obs, select, out)
+        obs, codes, want, unless, out = self._value_args(obs, select, out)
         sa, sb = self._starts(episode_start)
         rc = C.lib().pe_policy_value_lstm(self._handle(), obs.data_ptr(), int(codes), sa, sb, want, unless,
                                           out.data_ptr(), self._stream())
@@ -753,8 +691,7 @@ class RecurrentPolicy:
             if len(out) != len(self.towers) or any(len(pair) != 2 for pair in out):
                 raise ValueError(f"out must be {len(self.towers)} (h, c) pairs")
             for x in (x for pair in out for x in pair):
-                if not (type(x) is torch.Tensor and x.dtype is torch.float32 and x.is_cuda
-                        and x.get_device() == b._dev_index and x.is_contiguous() and tuple(x.shape) == shape):
+                if not _on_dev(x, b, (torch.float32,), shape):
                     raise ValueError(f"out tensors must be contiguous float32 of shape {shape} on {b.device}")
         res = []
         for i in range(len(self.towers)):

@@ -39,7 +39,7 @@ import numpy as np
 
 from . import _capi as C
 from .codes import CODE_POS, CODE_VIS, code_table, encode_obs
-from .policy import Policy, RecurrentPolicy
+from .policy import Policy, RecurrentPolicy, _on_dev
 
 U64 = 0xFFFFFFFFFFFFFFFF
 
@@ -266,8 +266,7 @@ class ReplayBatch:
         B, D = codes.shape
         if out is None:
             out = torch.empty((B, D), dtype=torch.float32, device=b.device)
-        elif not (type(out) is torch.Tensor and out.dtype is torch.float32 and out.is_cuda
-                  and out.get_device() == b._dev_index and out.is_contiguous() and tuple(out.shape) == (B, D)):
+        elif not _on_dev(out, b, (torch.float32,), (B, D)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(B, D)} on {b.device}")
         with torch.cuda.device(b.device):
             C.check(C.lib().pe_expand_obs_codes(b.handle, 1, B, _p(codes), 0, _p(out), None, None, None, b._stream()),
@@ -424,8 +423,7 @@ class ReplayCollector:
         B = mb.obs.shape[0]
         if out is None:
             out = mb.targets
-        elif not (type(out) is torch.Tensor and out.dtype is torch.float32 and out.is_cuda
-                  and out.get_device() == b._dev_index and out.is_contiguous() and tuple(out.shape) == (B,)):
+        elif not _on_dev(out, b, (torch.float32,), (B,)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(B,)} on {b.device}")
         target_policy.act_rows(mb.next_obs, out=(mb._next_actions, mb._next_q, None))
         target_device(mb._next_q, mb.rewards, mb.dones, gamma, out)

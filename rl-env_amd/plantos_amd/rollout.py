@@ -30,7 +30,7 @@ import ctypes
 import numpy as np
 
 from . import _capi as C
-from .policy import Policy, RecurrentPolicy, lstm_host_forward
+from .policy import Policy, RecurrentPolicy, _on_dev, lstm_host_forward
 
 ROW_ALIGN = 512  # bytes: every row of the buffer starts as aligned as a fresh torch allocation
 
@@ -247,9 +247,7 @@ class _Collector:
     def _obs_f32(self, out=None):
         torch, b = self._torch, self.batch
         T, n, D = self.n_steps, b.num_envs, b.obs_dim
-        if out is not None and not (type(out) is torch.Tensor and out.dtype is torch.float32 and out.is_cuda
-                                    and out.get_device() == b._dev_index and out.is_contiguous()
-                                    and tuple(out.shape) == (T * n, D)):
+        if out is not None and not _on_dev(out, b, (torch.float32,), (T * n, D)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(T * n, D)} on {b.device}")
         if not b.obs_codes:
             if out is None:

@@ -18,6 +18,17 @@ events, the order of the paths rotating from round to round; median, min and max
 rounds are reported (the spread).  No GPU: the tool fails.
 
   python tools/policy_rate.py [--out profiles/policy_rate.json] [--iters 50] [--rounds 9]
+
+--host-cost measures the host side of a call instead: 64 envs, the net [[32, 5], [32, 1]] (LSTM
+hidden 32), K back-to-back calls and one synchronize at the end, wall time / K, for Policy.act(),
+Policy.value(), RecurrentPolicy.act() and the bare ctypes pe_policy_forward (and, as *_issue, the
+time of the K calls alone: where the kernel takes longer than the host, the wall time is the kernel's).  One process is one
+round; --label names the side and --package-root the checkout whose plantos_amd is imported, so a
+driver alternates two checkouts on one machine.  --out then collects the rounds per label, with
+their medians and spread (max - min).
+
+  python tools/policy_rate.py --host-cost --label new --out profiles/policy_host_cost.json
+  python tools/policy_rate.py --host-cost --label parent --package-root <parent>/rl-env_amd --out ...
 """
 import argparse
 import ctypes
@@ -25,10 +36,10 @@ import json
 import os
 import statistics
 import sys
+import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, "rl-env_amd"))
 
 F32_MATRIX_PEAK = 157.3e12  # FLOP/s, v_mfma_f32_32x32x2_f32 on every CU at the peak clock
 GEOMETRY = dict(grid_size=20, num_plants=10, num_obstacles=12, lidar_range=6, lidar_channels=16)
@@ -45,17 +56,84 @@ def window(torch, fn, iters):
     return a.elapsed_time(b) * 1e-3 / iters
 
 
+HOST_COST_PATHS = ("policy_act", "policy_value", "recurrent_act", "ctypes_forward")
+
+
+def host_cost(args):
+    """one round: {path: microseconds per call}"""
+    import torch
+    from plantos_amd import PlantOSBatch, Policy, RecurrentPolicy
+    from plantos_amd import _capi as C
+    dev, towers, K = "cuda:0", [[32, 5], [32, 1]], args.calls
+    b = PlantOSBatch(64, seed=7, device=dev, obs_codes=True, **GEOMETRY)
+    b.reset()
+    act = torch.empty(64, dtype=torch.int32, device=dev)
+    for t in range(4):
+        b.synth_actions(7, t, out=act)
+        b.step(act)
+    pol, rec = Policy(b, towers), RecurrentPolicy(b, 32, towers)
+    P = ctypes.c_void_p
+    fwd, obs = C.lib().pe_policy_forward, P(b.obs.data_ptr())
+    outs = (P(pol.actions.data_ptr()), P(pol.logits.data_ptr()), P(pol.values.data_ptr()), b._stream())
+    paths = {"policy_act": pol.act, "policy_value": pol.value, "recurrent_act": rec.act,
+             "ctypes_forward": lambda: fwd(pol._p, obs, 1, 0, 0, 0, *outs)}
+    row = {}
+    for name in HOST_COST_PATHS:
+        fn = paths[name]
+        for _ in range(200):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(K):
+            fn()
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        row[name] = round((time.perf_counter() - t0) / K * 1e6, 3)
+        row[name + "_issue"] = round((t1 - t0) / K * 1e6, 3)  # the host's share: the calls alone, before the synchronize
+    pol.close()
+    rec.close()
+    b.close()
+    return row
+
+
+def host_cost_main(args):
+    row = host_cost(args)
+    print(json.dumps({"label": args.label, **row}))
+    if not args.out:
+        return
+    doc = {"tool": "policy_rate --host-cost", "envs": 64, "towers": [[32, 5], [32, 1]], "lstm_hidden": 32,
+           "calls_per_round": args.calls, "unit": "us per call (wall time / calls, one synchronize at the end)",
+           "rounds": {}}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            doc = json.load(f)
+    doc["rounds"].setdefault(args.label, []).append(row)
+    doc["summary"] = {lab: {k: {"median": statistics.median(r[k] for r in rs),
+                                "spread": round(max(r[k] for r in rs) - min(r[k] for r in rs), 3)}
+                            for k in rs[0]} for lab, rs in doc["rounds"].items()}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(doc, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--host-cost", action="store_true")
+    ap.add_argument("--calls", type=int, default=2000)
+    ap.add_argument("--label", default="new")
+    ap.add_argument("--package-root", default=os.path.join(REPO, "rl-env_amd"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--envs", type=int, nargs="*", default=[65536, 4096])
     args = ap.parse_args()
+    sys.path.insert(0, args.package_root)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("policy_rate: no GPU (a time cannot be measured on a CPU)")
+    if args.host_cost:
+        return host_cost_main(args)
     from plantos_amd import PlantOSBatch, Policy
     from plantos_amd import _capi as C
     L = C.lib()
