@@ -5,7 +5,7 @@ import os
 import numpy as np
 import torch
 
-from plantos_amd.codes import code_table
+from plantos_amd.codes import CODE_POS, CODE_VIS, code_table
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -30,12 +30,31 @@ def make_tensors(towers, D, seed, scale="std"):
     return out
 
 
-def obs_rows(D, n=37, seed=7):
+def geometry_codes(rng, rows, G, R, D):
+    """u8 [rows, D] of obs codes a (grid G, range R) geometry of D = 5C + 27 values can write, every
+    column from its own range: distances 0..R, one-hots 0 / R + 1, positions 96.., visits 80..90."""
+    C = (D - 27) // 5
+    assert D == 5 * C + 27 and C >= 1, D
+    out = np.zeros((rows, D), np.uint8)
+    lid = out[:, :5 * C].reshape(rows, C, 5)
+    lid[..., 0] = rng.integers(0, R + 1, (rows, C))
+    lid[..., 1:] = rng.integers(0, 2, (rows, C, 4)) * (R + 1)
+    out[:, 5 * C:5 * C + 2] = CODE_POS + rng.integers(0, G, (rows, 2))
+    out[:, 5 * C + 2:] = CODE_VIS + rng.integers(0, 11, (rows, 25))
+    return out
+
+
+def obs_rows(D, n=37, seed=7, geometry=None):
     """n obs rows: real env rows from the golden trajectories (spread over the rollout), then
-    uniform [0, 1) rows for the last third."""
+    uniform [0, 1) rows for the last third.  geometry = (G, R): the real rows are expanded from
+    that geometry's own code table instead (geometry_codes), for lengths without a trajectory."""
     rng = np.random.default_rng(seed)
     n_uni = n // 3
     n_real = n - n_uni
+    if geometry is not None:
+        G, R = geometry
+        real = code_table(G, R)[geometry_codes(rng, n_real, G, R, D)]
+        return np.ascontiguousarray(np.concatenate([real, rng.random((n_uni, D), np.float32)]).astype(np.float32))
     name = {107: "traj_g20_random.npz", 77: "traj_g21_explore.npz"}.get(D)
     path = os.path.join(GOLDEN, name) if name else None
     if path and os.path.exists(path):

@@ -20,11 +20,11 @@ N, T = 37, 12
 MARGIN = 8.0  # the twin's deviation from f64 <= MARGIN x torch-f32's (test_twin_against_f64)
 
 
-def sequence(D, seed=5):
+def sequence(D, seed=5, geometry=None):
     """xs f32 [T, N, D] (obs_rows' real and uniform rows, shuffled over the steps) and starts
     bool [T, N]: all set at t = 0, then random with p = 0.15."""
     rng = np.random.default_rng(seed)
-    x = obs_rows(D, n=N * T)
+    x = obs_rows(D, n=N * T, geometry=geometry)
     xs = np.ascontiguousarray(x[rng.permutation(N * T)].reshape(T, N, D))
     starts = rng.random((T, N)) < 0.15
     starts[0] = True
@@ -41,10 +41,15 @@ def test_twin_against_f64(H, D, scale):
     the deviation of torch's own f32 modules.  The margin: the sequential chain over K = D + H
     accumulates about sqrt(K) roundings where torch's blocked sums do not, and pe_tanhf is
     3.16 u against libm's < 1 u."""
+    check_twin_against_f64(H, D, scale)
+
+
+def check_twin_against_f64(H, D, scale, geometry=None):
+    """test_twin_against_f64's scheme; geometry = (G, R): obs rows of that geometry (obs_rows)."""
     sd = lstm_state_dict(D, H, seed=H + D, scale=scale)
     Hp, towers, act, lstm, mlp = P.parse_lstm_state_dict(sd)
     assert Hp == H and act == "tanh"
-    xs, starts = sequence(D)
+    xs, starts = sequence(D, geometry=geometry)
     ref64 = TorchRecurrent(D, H, lstm, mlp, torch.float64, N)
     ref32 = TorchRecurrent(D, H, lstm, mlp, torch.float32, N)
     states = None
