@@ -258,6 +258,7 @@ int pe_pystream_destroy(pe_pystream* s);
  * Scratch: (G*G + 2*max_depth + 2) * 4 + (n_simulations + 1) * 32 + 2504 bytes/env. */
 typedef struct pe_mcts pe_mcts;
 int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t max_depth, pe_mcts** out);
+/* Every pe_mcts_* call needs `h` alive, except pe_mcts_destroy, which may follow pe_destroy(h). */
 int pe_mcts_destroy(pe_mcts* m);
 /* np.random.seed(seeds[e]) for env e (HOST array of n, or NULL: base_seed + e). */
 int pe_mcts_seed(pe_mcts* m, const uint32_t* seeds, uint32_t base_seed, void* stream);
@@ -270,6 +271,11 @@ int pe_mcts_get_rng(pe_mcts* m, uint32_t* key, int32_t* pos);
  * -1 pad), visits i32[n,5], value f64[n,5].  Device pointers. */
 int pe_mcts_search(pe_mcts* m, const uint8_t* mask, int32_t* actions, int32_t* root_order, int32_t* root_visits,
                    double* root_value, void* stream);
+/* The search kernel pe_mcts_search launches for this handle, as a static string:
+ * "pe_mcts_search_lds_kernel" (sim envs in LDS: G <= 64 and 64 lanes' cell bytes and
+ * draw rings within 64 KiB, which holds up to G = 29) or "pe_mcts_search_kernel"
+ * (sim envs in global memory, any G). */
+int pe_mcts_kernel_name(pe_mcts* m, const char** name);
 
 /* rgb_array frames (PlantOSEnvNew.render with render_mode='rgb_array',
  * gradio-app/plantos_env_new.py:631-633, 697-762: the colour path taken when no sprite

@@ -35,6 +35,16 @@ class POMt(ctypes.Structure):
     _fields_ = [("mt", ctypes.c_uint32 * 624), ("index", ctypes.c_int32)]
 
 
+class POMctsStats(ctypes.Structure):
+    """po_mcts_stats (plantos_oracle.h): what one search exercised."""
+    _fields_ = [("max_path_nodes", ctypes.c_int32), ("moves_into_30", ctypes.c_int32),
+                ("moves_into_bumped_sat", ctypes.c_int32), ("select_ended", ctypes.c_int32),
+                ("select_depth_stop", ctypes.c_int32), ("waters_thirsty", ctypes.c_int32)]
+
+
+MCTS_STATS = tuple(f[0] for f in POMctsStats._fields_)
+
+
 def build():
     subprocess.run(["make", "-s", "-C", HERE], check=True)
 
@@ -76,6 +86,8 @@ def lib():
         L.po_mcts_search.argtypes = [ctypes.POINTER(POConfig), P, P, P, P, ctypes.POINTER(POMt), ctypes.c_int32,
                                      ctypes.c_double, ctypes.c_int32, P, P, P]
         L.po_mcts_search.restype = ctypes.c_int32
+        L.po_mcts_search_stats.argtypes = L.po_mcts_search.argtypes + [ctypes.POINTER(POMctsStats)]
+        L.po_mcts_search_stats.restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -132,9 +144,10 @@ class NpMT:
         return lib().po_np_randint(ctypes.byref(self.s), n)
 
 
-def mcts_search(cfg, cells, visits, explored, scal, rng, n_sims, c_param, max_depth):
+def mcts_search(cfg, cells, visits, explored, scal, rng, n_sims, c_param, max_depth, stats=False):
     """MCTS.search (mcts_custom_trainer.py:91-139) of one env; rng (NpMT) advances.
-    Returns (action, order[5], visits[5], value[5]) -- root children in insertion order."""
+    Returns (action, order[5], visits[5], value[5]) -- root children in insertion order;
+    with stats=True also a dict of what the search exercised (MCTS_STATS, po_mcts_stats)."""
     cells = np.ascontiguousarray(cells, np.uint8)
     visits = np.ascontiguousarray(visits, np.int32)
     explored = np.ascontiguousarray(explored, np.int8)
@@ -143,6 +156,12 @@ def mcts_search(cfg, cells, visits, explored, scal, rng, n_sims, c_param, max_de
     order = np.zeros(5, np.int32)
     cv = np.zeros(5, np.int32)
     cval = np.zeros(5, np.float64)
+    if stats:
+        st = POMctsStats()
+        a = lib().po_mcts_search_stats(ctypes.byref(cfg), _p(cells), _p(visits), _p(explored), _p(sc),
+                                       ctypes.byref(rng.s), n_sims, c_param, max_depth, _p(order), _p(cv), _p(cval),
+                                       ctypes.byref(st))
+        return a, order, cv, cval, {k: int(getattr(st, k)) for k in MCTS_STATS}
     a = lib().po_mcts_search(ctypes.byref(cfg), _p(cells), _p(visits), _p(explored), _p(sc), ctypes.byref(rng.s),
                              n_sims, c_param, max_depth, _p(order), _p(cv), _p(cval))
     return a, order, cv, cval

@@ -54,6 +54,9 @@ typedef struct {
     int32_t* visits;
     int8_t* explored;
     int32_t scal[PO_NSCAL];
+    po_mcts_stats* st; /* NULL: nothing is counted */
+    int32_t* bumped;   /* [G*G] 1 + index of the last simulation that moved into the cell (stats only) */
+    int32_t sim;
 } sim_t;
 
 static double pct_of(const po_config* c, const sim_t* s) {
@@ -62,8 +65,26 @@ static double pct_of(const po_config* c, const sim_t* s) {
     return ((double)info[3] / (double)info[4]) * 100.0;
 }
 
+/* What the step about to be taken exercises (po_mcts_stats); reads the state, changes none of it. */
+static void count_step(sim_t* s, int a) {
+    static const int D[4][2] = {{-1, 0}, {0, 1}, {1, 0}, {0, -1}};
+    const int G = s->c->grid_size, x = s->scal[PO_S_X], y = s->scal[PO_S_Y];
+    if (a < 4) {
+        const int nx = x + D[a][0], ny = y + D[a][1];
+        if (0 <= nx && nx < G && 0 <= ny && ny < G && s->cells[nx * G + ny] != 1) {
+            const int k = nx * G + ny;
+            if (s->visits[k] == 30) s->st->moves_into_30 += 1;
+            if (s->visits[k] >= 31 && s->bumped[k] == s->sim + 1) s->st->moves_into_bumped_sat += 1;
+            s->bumped[k] = s->sim + 1;
+        }
+    } else if (s->cells[x * G + y] == 3) {
+        s->st->waters_thirsty += 1;
+    }
+}
+
 static double sim_step(sim_t* s, int a, uint8_t* te, uint8_t* tr) {
     double r;
+    if (s->st) count_step(s, a);
     po_step(s->c, s->cells, s->visits, s->explored, s->scal, a, NULL, &r, te, tr);
     return r;
 }
@@ -90,6 +111,14 @@ static int heuristic(const sim_t* s, po_mt* rng) {
 int32_t po_mcts_search(const po_config* c, const uint8_t* cells, const int32_t* visits, const int8_t* explored,
                        const int32_t* scal, po_mt* rng, int32_t n_sims, double c_param, int32_t max_depth,
                        int32_t* order, int32_t* cvisits, double* cvalue) {
+    return po_mcts_search_stats(c, cells, visits, explored, scal, rng, n_sims, c_param, max_depth, order, cvisits,
+                                cvalue, NULL);
+}
+
+int32_t po_mcts_search_stats(const po_config* c, const uint8_t* cells, const int32_t* visits,
+                             const int8_t* explored, const int32_t* scal, po_mt* rng, int32_t n_sims,
+                             double c_param, int32_t max_depth, int32_t* order, int32_t* cvisits, double* cvalue,
+                             po_mcts_stats* stats) {
     const int GG = c->grid_size * c->grid_size;
     node_t* nodes = (node_t*)calloc((size_t)n_sims + 1, sizeof(node_t));
     int nn = 1;
@@ -102,6 +131,9 @@ int32_t po_mcts_search(const po_config* c, const uint8_t* cells, const int32_t* 
     s.cells = (uint8_t*)malloc(GG);
     s.visits = (int32_t*)malloc(GG * sizeof(int32_t));
     s.explored = (int8_t*)malloc(GG);
+    s.st = stats;
+    s.bumped = stats ? (int32_t*)calloc((size_t)GG, sizeof(int32_t)) : NULL;
+    if (stats) memset(stats, 0, sizeof(*stats));
     for (int sim = 0; sim < n_sims; ++sim) {
         /* _copy_env_state :221-243 */
         memcpy(s.cells, cells, GG);
@@ -111,6 +143,7 @@ int32_t po_mcts_search(const po_config* c, const uint8_t* cells, const int32_t* 
         s.scal[PO_S_X] = scal[PO_S_X];
         s.scal[PO_S_Y] = scal[PO_S_Y];
         s.scal[PO_S_STEP] = scal[PO_S_STEP];
+        s.sim = sim;
         int node = 0, depth = 0;
         uint8_t te = 0, tr = 0;
         /* 1. selection :106-114 */
@@ -136,8 +169,12 @@ int32_t po_mcts_search(const po_config* c, const uint8_t* cells, const int32_t* 
             node = best;
             sim_step(&s, nodes[node].action, &te, &tr);
             depth += 1;
-            if (te || tr) break;
+            if (te || tr) {
+                if (stats) stats->select_ended += 1;
+                break;
+            }
         }
+        if (stats && depth >= max_depth) stats->select_depth_stop += 1; /* nothing to expand or roll out */
         /* 2. expansion :117-125 (depth is not advanced) */
         if (nodes[node].nun > 0 && depth < max_depth) {
             node_t* p = &nodes[node];
@@ -167,10 +204,13 @@ int32_t po_mcts_search(const po_config* c, const uint8_t* cells, const int32_t* 
             }
         }
         /* 4. backpropagation :130-134 */
+        int plen = 0;
         for (int n = node; n >= 0; n = nodes[n].parent) {
             nodes[n].visits += 1;
             nodes[n].value += total;
+            plen += 1;
         }
+        if (stats && plen > stats->max_path_nodes) stats->max_path_nodes = plen;
     }
     int32_t act;
     const node_t* root = &nodes[0];
@@ -199,6 +239,7 @@ int32_t po_mcts_search(const po_config* c, const uint8_t* cells, const int32_t* 
     free(s.cells);
     free(s.visits);
     free(s.explored);
+    free(s.bumped);
     free(nodes);
     return act;
 }

@@ -904,6 +904,7 @@ constexpr size_t kMctsLdsMax = 64 * 1024;  // >= 2 workgroups per CU
 
 struct pe_mcts {
   pe_handle* h;
+  int device;  // h->device, kept so that pe_mcts_destroy needs nothing of a handle destroyed before it
   int n_sims, max_depth;
   double c;
   void* mem;
@@ -918,7 +919,32 @@ struct pe_mcts {
   double* logt;
 };
 
+// Which search kernel a handle of grid side G runs.  The LDS kernel needs, per
+// workgroup of 64 lanes, each lane's cell bytes (G*G rounded up to whole dwords, one
+// more dword when that count is even: odd dword stride between lanes) and its draw
+// ring; it runs when G <= 64 and that fits kMctsLdsMax, else cells stay in global memory.
+struct MctsKernelChoice {
+  bool use_lds;
+  int ldsp;     // LDS bytes of one lane's cells
+  size_t lds;   // dynamic LDS bytes of a workgroup
+};
+
+static MctsKernelChoice mcts_kernel_choice(const Geo& g) {
+  MctsKernelChoice k;
+  k.ldsp = (g.GG + 3) / 4 * 4;
+  if ((k.ldsp / 4) % 2 == 0) k.ldsp += 4;  // odd dword stride between lanes
+  k.lds = 64 * ((size_t)k.ldsp + 4 * (size_t)kRing);
+  k.use_lds = g.G <= 64 && k.lds <= kMctsLdsMax;
+  return k;
+}
+
 extern "C" {
+
+int pe_mcts_kernel_name(pe_mcts* m, const char** name) {
+  if (!m || !name) return fail(PE_ERR_ARG, "null argument");
+  *name = mcts_kernel_choice(m->h->g).use_lds ? "pe_mcts_search_lds_kernel" : "pe_mcts_search_kernel";
+  return PE_OK;
+}
 
 int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t max_depth, pe_mcts** out) {
   if (!h || !out) return fail(PE_ERR_ARG, "null argument");
@@ -953,6 +979,7 @@ int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t 
   m->csg = reinterpret_cast<uint32_t*>(q + al(n * ggp) + al(n * GG * 4));
   m->ggp = (int)ggp;
   m->h = h;
+  m->device = h->device;
   m->n_sims = n_simulations;
   m->max_depth = max_depth;
   m->c = c_param;
@@ -977,7 +1004,7 @@ int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t 
 
 int pe_mcts_destroy(pe_mcts* m) {
   if (!m) return PE_OK;
-  DeviceGuard dg(m->h->device);
+  DeviceGuard dg(m->device);  // not m->h->device: the env handle may be gone already
   hipError_t e = hipFree(m->mem);
   delete m;
   return e == hipSuccess ? PE_OK : hip_fail(e, "hipFree");
@@ -1062,16 +1089,15 @@ int pe_mcts_search(pe_mcts* m, const uint8_t* mask, int32_t* actions, int32_t* r
   a.rvalue = root_value;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t cells = (int64_t)h->n * h->g.GG;
-  int ldsp = (h->g.GG + 3) / 4 * 4;
-  if ((ldsp / 4) % 2 == 0) ldsp += 4;  // odd dword stride between lanes
-  const size_t lds = 64 * ((size_t)ldsp + 4 * (size_t)kRing);
-  const bool use_lds = h->g.G <= 64 && lds <= kMctsLdsMax;
+  const MctsKernelChoice kc = mcts_kernel_choice(h->g);
+  const bool use_lds = kc.use_lds;
+  const size_t lds = kc.lds;
   if (use_lds) {
     a.cellb = m->cellb;
     a.csim = m->csim;
     a.csg = m->csg;
     a.ggp = m->ggp;
-    a.ldsp = ldsp;
+    a.ldsp = kc.ldsp;
   }
   if (cells > 0) {
     // the steps' deferred visit-overflow writes first: the clone reads the exact counts

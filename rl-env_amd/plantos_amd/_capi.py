@@ -40,6 +40,7 @@ EXPORTS = [
     "pe_pystream_create", "pe_pystream_next", "pe_pystream_getrandbits32", "pe_pystream_destroy",
     "pe_curriculum_enable", "pe_curriculum_disable", "pe_curriculum_get",
     "pe_mcts_create", "pe_mcts_destroy", "pe_mcts_seed", "pe_mcts_set_rng", "pe_mcts_get_rng", "pe_mcts_search",
+    "pe_mcts_kernel_name",
     "pe_step_codes", "pe_obs_code_table", "pe_expand_obs_codes",
     "pe_render_tables", "pe_render",
     "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward", "pe_policy_forward_host",
@@ -175,6 +176,8 @@ def lib():
     L.pe_mcts_set_rng.argtypes = [P, P, P]
     L.pe_mcts_get_rng.argtypes = [P, P, P]
     L.pe_mcts_search.argtypes = [P, P, P, P, P, P, P]
+    L.pe_mcts_kernel_name.argtypes = [P, ctypes.POINTER(ctypes.c_char_p)]
+    L.pe_mcts_kernel_name.restype = ctypes.c_int
     if hasattr(L, "pe_render"):  # (an older library loaded for a same-box A/B lacks them)
         L.pe_render_tables.argtypes = [CP, I32, P, P]
         L.pe_render.argtypes = [P, I32, P, I32, P, ctypes.c_int64, ctypes.c_int64, P]

@@ -45,6 +45,14 @@ class MCTS:
         self.root_value = torch.zeros((n, 5), dtype=torch.float64, device=dev)
         self.seed(seed)
 
+    @property
+    def kernel_name(self):
+        """The search kernel this handle runs: 'pe_mcts_search_lds_kernel' (sim envs in
+        LDS, grids up to 29x29) or 'pe_mcts_search_kernel' (sim envs in global memory)."""
+        name = ctypes.c_char_p()
+        C.check(C.lib().pe_mcts_kernel_name(self._h, ctypes.byref(name)), "pe_mcts_kernel_name")
+        return name.value.decode()
+
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.batch.device).cuda_stream)
 

@@ -19,7 +19,11 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-MCTS_FILES = ["mcts_g7", "mcts_g20", "mcts_g25", "mcts_g20d"]
+MCTS_FILES = ["mcts_g7", "mcts_g20", "mcts_g25", "mcts_g20d", "mcts_g32"]
+# which search kernel a fixture's geometry runs (sim cells in LDS up to 29x29, see pe_mcts_kernel_name)
+MCTS_KERNELS = {"mcts_g7": "pe_mcts_search_lds_kernel", "mcts_g20": "pe_mcts_search_lds_kernel",
+                "mcts_g25": "pe_mcts_search_lds_kernel", "mcts_g20d": "pe_mcts_search_lds_kernel",
+                "mcts_g32": "pe_mcts_search_kernel"}
 
 
 def make(cfg, n, **kw):
@@ -56,6 +60,7 @@ def test_mcts_matches_reference_searches(name):
     b.set_state(cells=f["cells"][first], visits=f["visits"][first], explored=f["explored"][first], scalars=scal)
     m = MCTS(b, n_simulations=int(f["n_sims"]), c_param=float(f["c_param"]), max_depth=int(f["max_depth"]),
              seed=f["cseed"][first].astype(np.uint32))
+    assert m.kernel_name == MCTS_KERNELS[name]
     depth = max(len(r) for r in rows)
     for d in range(depth):
         live = np.array([len(r) > d for r in rows])

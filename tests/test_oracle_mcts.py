@@ -13,7 +13,7 @@ import pytest
 from golden_util import cfg_tuple, load
 from oracle import oracle as O
 
-MCTS_FILES = ["mcts_g7", "mcts_g20", "mcts_g25", "mcts_g20d"]
+MCTS_FILES = ["mcts_g7", "mcts_g20", "mcts_g25", "mcts_g20d", "mcts_g32"]
 
 
 def test_numpy_legacy_stream():

@@ -726,6 +726,7 @@ def main_mcts():
     gen_mcts("g20", "g20", 50, 100, 3, 12, 600, inject_cases=24)
     gen_mcts("g25", "g25", 50, 100, 1, 8, 700)
     gen_mcts("g20d", "g20", 100, 50, 1, 4, 800)
+    gen_mcts("g32", "g32", 30, 40, 2, 5, 900, inject_cases=8)  # above the LDS limit: pe_mcts_search_kernel
 
 
 def main_curriculum_tc():
