@@ -1,39 +1,29 @@
 """The batched CurriculumWrapper through the step kernels' OWN auto-resets (device-rng
-maps: prefetched records, the wave-cooperative reset, the byte-coded 64x64 sector
-kernel, the one-wave-per-env kernel), with desynchronized episodes, against the CPU
-wrapper restatement that tests/test_oracle_curriculum.py pins to the reference's
-classes (A2C_training.py:37-109: a threshold hit terminates; trainingCode.py:24-98:
-it only marks the maze completed, 50 episodes per maze).  Every step: obs (incl. the
-stale reset obs and carried visit slices), reward, terminated, truncated, terminal
-obs; at the end: thresholds, counters, visit counts, cells, scalars."""
+maps: prefetched records, the wave-cooperative reset) on three kernels -- the 16-env
+headline sector kernel, the byte-coded 64x64 sector kernel and the far kernel --, with
+desynchronized episodes of the reference's length (1000 steps) and wrapper defaults but
+low thresholds, against the CPU wrapper restatement that tests/test_oracle_curriculum.py
+pins to the reference's classes (A2C_training.py:37-109: a threshold hit terminates;
+trainingCode.py:24-98: it only marks the maze completed, 50 episodes per maze).  Every
+step: obs (incl. the stale reset obs and carried visit slices), reward, terminated,
+truncated, terminal obs; at the end: thresholds, counters, visit counts, cells, scalars.
+(Every other kernel family, time-outs, the threshold ladder, carried counts past 15 and
+the masked reset: tests/test_gpu_curriculum_kernels.py.)"""
 import numpy as np
 import pytest
 import torch
 
+from curriculum_cases import PhiloxCurriculumVec
 from oracle import oracle as O
 from test_oracle_curriculum import OracleCurriculumVec
 
 pytestmark = pytest.mark.gpu
 
 CFG = {
-    "g20": (20, 10, 12, 6, 16),       # pe_step_quad<C16,R6,1word> (f32 tile, prefetched records)
-    "g64": (64, 100, 120, 6, 64),     # pe_step_quad<C64,R6> (byte-coded tile, LDS-DMA staged records)
+    "g20": (20, 10, 12, 6, 16),       # pe_step_quad<C16,R6,1word,W8,E16> (f32 tile, prefetched records)
+    "g64": (64, 100, 120, 6, 64),     # pe_step_quad<C64,R6,bytetile> (byte-coded tile, LDS-DMA staged records)
     "g64r32": (64, 100, 120, 32, 64),  # pe_step_far
 }
-
-
-class PhiloxCurriculumVec(OracleCurriculumVec):
-    """The same wrapper over the device-rng map stream: env e's k-th map is
-    reset_philox(seed, e, k) (what pe_create / pe_reset / the auto-reset draw)."""
-
-    def __init__(self, cfg, n, seed, **kw):
-        super().__init__(cfg, n, 0, **kw)
-        self.seed = seed
-        for e in range(n):
-            self.b.reset_philox(e, seed, e, 0)  # pe_create
-
-    def _new_map(self, e):
-        self.b.reset_philox(e, self.seed, e, int(self.b.scal[e, O.S_EPISODE]))
 
 
 @pytest.mark.parametrize("variant", ["a2c", "trainingCode"])
