@@ -496,6 +496,43 @@ int pe_policy_value_lstm(pe_policy* p, const void* obs, int32_t obs_is_codes, co
                          const uint8_t* start_b_or_null, const uint8_t* want_or_null, const uint8_t* unless_or_null,
                          float* values, void* stream);
 
+/* Reduced-precision policy inference: the MLP policy of "Policy inference" with bf16 operands
+ * and f32 accumulation (v_mfma_f32_32x32x16_bf16).  Opt-in per policy; PE_PREC_F32 is the
+ * definition of "Policy inference" unchanged.  Recurrent policies have no reduced precision.
+ *
+ * Definition (the host twin pe_policy_forward_host_bf16 executes it; a PE_PREC_BF16 policy
+ * has the towers, shapes, activation, heads, argmax and sampler of "Policy inference", with
+ * these differences):
+ *  - Operand rounding: an obs value (tab[code] or the f32 obs entry), a hidden-layer weight
+ *    and a hidden activation after pe_tanhf / pe_relu are each rounded to bf16 once, to
+ *    nearest even.
+ *  - Biases, head weights and all outputs stay f32.
+ *  - Hidden pre-activation: z_j = f32(b_j + sum_k w[j][k] x[k]) over the bf16 operands,
+ *    accumulated in f32 by the MFMA.  The products are exact in f32; the order and the
+ *    internal rounding of the sum are the hardware's and are not defined.  The host twin
+ *    computes the sum in f64 and rounds it to f32 once.
+ *  - Head: the f32 fmaf chain in k order of "Policy inference" over the (bf16-valued) last
+ *    hidden activations: given those activations it is defined bit for bit.
+ *  - Consequence: where every partial sum of a pre-activation is exactly representable in
+ *    f32, kernel and twin agree bit for bit.  Elsewhere a pre-activation may differ by f32
+ *    summation error, which after the activation's bf16 rounding occasionally moves one
+ *    hidden unit by one bf16 ulp.
+ * pe_policy_load, pe_policy_forward, pe_policy_forward_rows and pe_policy_value serve a policy
+ * of either precision with the same arguments and the same checks; within one precision every
+ * env tile, pe_policy_forward_rows and pe_policy_value give the same bits. */
+enum pe_precision { PE_PREC_F32 = 0, PE_PREC_BF16 = 1 };
+/* pe_policy_create with a precision (pe_policy_create is PE_PREC_F32); PE_ERR_ARG for any
+ * other value, and if the tile's bf16 images do not fit the 160 KiB of LDS. */
+int pe_policy_create_prec(pe_handle* h, int32_t n_towers, const pe_policy_tower* shapes, int32_t activation,
+                          int32_t env_tile, int32_t precision, pe_policy** out);
+/* The precision a policy was created with (PE_PREC_F32 for a recurrent one); -1 for NULL. */
+int32_t pe_policy_precision(const pe_policy* p);
+/* The host twin of a PE_PREC_BF16 policy: arguments as pe_policy_forward_host. */
+int pe_policy_forward_host_bf16(int32_t n, int32_t D, int32_t n_towers, const pe_policy_tower* towers,
+                                int32_t activation, const float* obs, int32_t mode, uint64_t seed,
+                                uint32_t env_id_offset, uint32_t t, int32_t* actions, float* head0_or_null,
+                                float* head1_or_null);
+
 /* Rollout collection: what SB3 2.2.1's OnPolicyAlgorithm.collect_rollouts and
  * RolloutBuffer.compute_returns_and_advantage add to the act / step loop (A2C(n_steps=5,
  * gamma=0.99, gae_lambda=1.0) A2C_training.py:229-247; the PPO family with n_steps=1024,

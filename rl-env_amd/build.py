@@ -24,12 +24,13 @@ SRC_RENDER = os.path.join(HERE, "csrc", "pe_render.hip")
 SRC_POLICY = os.path.join(HERE, "csrc", "pe_policy.hip")
 SRC_POLICY_HOST = os.path.join(HERE, "csrc", "pe_policy_host.cpp")
 SRC_POLICY_LSTM = os.path.join(HERE, "csrc", "pe_policy_lstm.hip")
+SRC_POLICY_BF16 = os.path.join(HERE, "csrc", "pe_policy_bf16.hip")
 SRC_ROLLOUT = os.path.join(HERE, "csrc", "pe_rollout.hip")
 SRC_ROLLOUT_HOST = os.path.join(HERE, "csrc", "pe_rollout_host.cpp")
 SRC_REPLAY = os.path.join(HERE, "csrc", "pe_replay.hip")
 SRC_REPLAY_HOST = os.path.join(HERE, "csrc", "pe_replay_host.cpp")
 SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST, SRC_POLICY_LSTM, SRC_ROLLOUT,
-           SRC_ROLLOUT_HOST, SRC_REPLAY, SRC_REPLAY_HOST]
+           SRC_ROLLOUT_HOST, SRC_REPLAY, SRC_REPLAY_HOST, SRC_POLICY_BF16]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in
                   ("pe_device.hpp", "pe_fast.hpp", "pe_quad.hpp", "pe_coop.hpp", "pe_handle.hpp", "pe_far.hpp",
                    "pe_plan.hpp", "pe_host.hpp", "pe_policy_math.hpp", "pe_policy_impl.hpp", "pe_policy_plan.hpp",

@@ -77,5 +77,11 @@ struct pe_policy_plan_info {
 extern "C" int pe_internal_policy_plan(int32_t D, int32_t n_envs, int32_t num_cus, int32_t n_towers,
                                        const pe_policy_lstm* lstms, const pe_policy_tower* shapes, int32_t activation,
                                        int32_t env_tile, pe_policy_plan_info* out);
+// ... for a precision (pe_policy_create_prec; PE_PREC_F32 answers as pe_internal_policy_plan;
+// lstms with another precision is PE_ERR_ARG).
+extern "C" int pe_internal_policy_plan_prec(int32_t D, int32_t n_envs, int32_t num_cus, int32_t n_towers,
+                                            const pe_policy_lstm* lstms, const pe_policy_tower* shapes,
+                                            int32_t activation, int32_t env_tile, int32_t precision,
+                                            pe_policy_plan_info* out);
 // pe_internal_render_free (pe_render.hip): frees the handle's render tables (pe_destroy).
 extern "C" void pe_internal_render_free(pe_handle* h);

@@ -138,6 +138,17 @@ FwdArgs fwd_args(const pe_policy* p, const void* obs, int32_t obs_is_codes) {
 
 }  // namespace
 
+// The PE_PREC_BF16 side (pe_policy_bf16.hip); the arguments are checked here.
+extern "C" {
+int pe_internal_policy_bf16_create(pe_handle* h, const PolicyPlan* plan, pe_policy** out);
+int pe_internal_policy_bf16_load(pe_policy* p, const pe_policy_tower* towers, void* stream);
+int pe_internal_policy_bf16_forward(pe_policy* p, int32_t rows, const void* obs, int32_t obs_is_codes, int32_t mode,
+                                    uint64_t seed, uint32_t t, int32_t* actions, float* head0, float* head1,
+                                    void* stream, const char* what);
+int pe_internal_policy_bf16_value(pe_policy* p, const void* obs, int32_t obs_is_codes, const uint8_t* want,
+                                  const uint8_t* unless, float* values, void* stream);
+}
+
 extern "C" {
 
 int pe_internal_policy_plan(int32_t D, int32_t n_envs, int32_t num_cus, int32_t n_towers, const pe_policy_lstm* lstms,
@@ -152,15 +163,38 @@ int pe_internal_policy_plan(int32_t D, int32_t n_envs, int32_t num_cus, int32_t 
   return PE_OK;
 }
 
-int pe_policy_create(pe_handle* h, int32_t n_towers, const pe_policy_tower* shapes, int32_t activation,
-                     int32_t env_tile, pe_policy** out) {
+int pe_internal_policy_plan_prec(int32_t D, int32_t n_envs, int32_t num_cus, int32_t n_towers,
+                                 const pe_policy_lstm* lstms, const pe_policy_tower* shapes, int32_t activation,
+                                 int32_t env_tile, int32_t precision, pe_policy_plan_info* out) {
+  if (!out) return fail(PE_ERR_ARG, "null argument");
+  if (lstms) {
+    if (precision != PE_PREC_F32) return fail(PE_ERR_ARG, "a recurrent policy has no reduced precision");
+    return pe_internal_policy_plan(D, n_envs, num_cus, n_towers, lstms, shapes, activation, env_tile, out);
+  }
+  PolicyPlan plan;
+  if (const int rc = make_policy_plan_prec(D, n_envs, num_cus, n_towers, shapes, activation, env_tile, precision, &plan))
+    return rc;
+  *out = {plan.env_tile, (uint64_t)plan.lds, (uint64_t)plan.n_packed, (uint64_t)plan.n_state};
+  return PE_OK;
+}
+
+int pe_policy_create_prec(pe_handle* h, int32_t n_towers, const pe_policy_tower* shapes, int32_t activation,
+                          int32_t env_tile, int32_t precision, pe_policy** out) {
   if (!h || !out) return fail(PE_ERR_ARG, "null argument");
   PolicyPlan plan;
-  if (const int rc = make_policy_plan(h->g.D, h->n, h->num_cus, n_towers, nullptr, shapes, activation, env_tile, false,
-                                      &plan))
+  if (const int rc = make_policy_plan_prec(h->g.D, h->n, h->num_cus, n_towers, shapes, activation, env_tile, precision,
+                                           &plan))
     return rc;
+  if (plan.precision == PE_PREC_BF16) return pe_internal_policy_bf16_create(h, &plan, out);
   return create_policy(h, plan, {kForward.of(plan), n_towers == 2 ? kValue.of(plan) : nullptr}, "pe_policy_create", out);
 }
+
+int pe_policy_create(pe_handle* h, int32_t n_towers, const pe_policy_tower* shapes, int32_t activation,
+                     int32_t env_tile, pe_policy** out) {
+  return pe_policy_create_prec(h, n_towers, shapes, activation, env_tile, PE_PREC_F32, out);
+}
+
+int32_t pe_policy_precision(const pe_policy* p) { return p ? p->precision : -1; }
 
 int pe_policy_destroy(pe_policy* p) {
   if (!p) return PE_OK;
@@ -174,6 +208,7 @@ int32_t pe_policy_env_tile(const pe_policy* p) { return p ? p->env_tile : 0; }
 int pe_policy_load(pe_policy* p, const pe_policy_tower* towers, void* stream) {
   if (!p || !towers) return fail(PE_ERR_ARG, "null argument");
   if (p->H) return fail(PE_ERR_ARG, "a recurrent policy is loaded with pe_policy_load_lstm");
+  if (p->precision == PE_PREC_BF16) return pe_internal_policy_bf16_load(p, towers, stream);
   PackArgs a;
   int nl = 0;
   uint32_t most = 0;
@@ -191,6 +226,9 @@ int pe_policy_forward(pe_policy* p, const void* obs, int32_t obs_is_codes, int32
   if (const int rc = check_forward(p, false, obs, actions, obs_is_codes, mode, head1,
                                    "a recurrent policy runs with pe_policy_forward_lstm"))
     return rc;
+  if (p->precision == PE_PREC_BF16)
+    return pe_internal_policy_bf16_forward(p, p->h->n, obs, obs_is_codes, mode, seed, t, actions, head0, head1, stream,
+                                           "pe_policy_forward");
   FwdArgs a = fwd_args(p, obs, obs_is_codes);
   a.mode = mode;
   a.seed = seed;
@@ -207,6 +245,9 @@ int pe_policy_forward_rows(pe_policy* p, int32_t rows, const void* obs, int32_t 
                                    "pe_policy_forward_rows does not evaluate a recurrent policy"))
     return rc;
   if (rows < 1) return fail(PE_ERR_ARG, "rows must be >= 1, got " + std::to_string(rows));
+  if (p->precision == PE_PREC_BF16)
+    return pe_internal_policy_bf16_forward(p, rows, obs, obs_is_codes, PE_POLICY_ARGMAX, 0, 0, actions, head0, head1,
+                                           stream, "pe_policy_forward_rows");
   FwdArgs a = fwd_args(p, obs, obs_is_codes);
   a.n = rows;  // the kernel bounds its last tile, its loads and its stores by a.n
   a.mode = PE_POLICY_ARGMAX;
@@ -222,6 +263,7 @@ int pe_policy_value(pe_policy* p, const void* obs, int32_t obs_is_codes, const u
                                    "a recurrent policy runs with pe_policy_value_lstm"))
     return rc;
   if (p->n_towers < 2) return fail(PE_ERR_ARG, "values need a second tower");
+  if (p->precision == PE_PREC_BF16) return pe_internal_policy_bf16_value(p, obs, obs_is_codes, want, unless, values, stream);
   const FwdArgs a = fwd_args(p, obs, obs_is_codes);
   return kValue.launch(p, a.n, stream, "pe_policy_value", a, ValueSel{want, unless, values});
 }

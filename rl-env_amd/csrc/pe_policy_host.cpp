@@ -2,6 +2,8 @@
 // (include/plantos_batch.h, "Policy inference" and "Recurrent policy inference"): the
 // definitions executed literally, one fmaf chain per pre-activation in ascending k,
 // pe_tanhf / pe_sigmoidf / pe_expf / the sampler from the header the kernels include too.
+// pe_policy_forward_host_bf16 is the twin of a PE_PREC_BF16 policy ("Reduced-precision policy
+// inference"): operands rounded to bf16, hidden sums in f64 rounded to f32 once, the f32 head chain.
 // Plain C++: no handle, no device.
 #include <cstring>
 #include <string>
@@ -164,9 +166,78 @@ void lstm_step(const pe_policy_lstm& L, int D, const float* x, bool start, float
     lstm_body<false>(L, D, x, start, h, c);
 }
 
+// x rounded to bf16, to nearest even, as an f32 (what v_cvt_pk_bf16_f32 gives; NaN stays NaN).
+inline float bf16_round(float x) {
+  uint32_t u = float_to_bits(x);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return bits_to_float(u | 0x00400000u);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return bits_to_float(u & 0xFFFF0000u);
+}
+
+// One tower of a PE_PREC_BF16 policy on one obs row xb (already bf16-valued); wb[l]: the
+// hidden layers' weights, bf16-valued.  A hidden pre-activation is the f64 sum rounded to f32
+// once; the head is tower_body's fmaf chain.
+void tower_forward_bf16(const pe_policy_tower& t, const std::vector<float>* wb, int D, int activation, const float* xb,
+                        float* out) {
+  float a[512], b[512];
+  const float* in = xb;
+  int K = D;
+  float* cur = a;
+  for (int l = 0; l < t.n_hidden; ++l) {
+    const int N = t.hidden[l];
+    for (int j = 0; j < N; ++j) {
+      const float* w = wb[l].data() + (size_t)j * K;
+      double s = (double)t.bias[l][j];
+      for (int k = 0; k < K; ++k) s += (double)w[k] * (double)in[k];
+      const float z = (float)s;
+      cur[j] = bf16_round(activation == PE_ACT_TANH ? pe_tanhf(z) : pe_relu(z));
+    }
+    in = cur;
+    K = N;
+    cur = cur == a ? b : a;
+  }
+  const int l = t.n_hidden;
+  for (int j = 0; j < t.n_out; ++j) out[j] = chain<false>(t.weight[l] + (size_t)j * K, in, K, t.bias[l][j]);
+}
+
 }  // namespace
 
 extern "C" {
+
+int pe_policy_forward_host_bf16(int32_t n, int32_t D, int32_t n_towers, const pe_policy_tower* towers,
+                                int32_t activation, const float* obs, int32_t mode, uint64_t seed,
+                                uint32_t env_id_offset, uint32_t t, int32_t* actions, float* head0, float* head1) {
+  if (const int rc = pe_internal_policy_check(n_towers, towers, activation, 1)) return rc;
+  if (n < 0 || D < 1 || !obs || !actions) return pe_internal_set_error(PE_ERR_ARG, "bad n / D or null obs / actions");
+  if (mode != PE_POLICY_ARGMAX && mode != PE_POLICY_SAMPLE)
+    return pe_internal_set_error(PE_ERR_ARG, "mode must be PE_POLICY_ARGMAX or PE_POLICY_SAMPLE");
+  if (head1 && n_towers < 2) return pe_internal_set_error(PE_ERR_ARG, "head1 needs a second tower");
+  std::vector<float> wb[2][3];
+  for (int i = 0; i < n_towers; ++i) {
+    int K = D;
+    for (int l = 0; l < towers[i].n_hidden; ++l) {
+      const size_t cnt = (size_t)towers[i].hidden[l] * K;
+      wb[i][l].resize(cnt);
+      for (size_t q = 0; q < cnt; ++q) wb[i][l][q] = bf16_round(towers[i].weight[l][q]);
+      K = towers[i].hidden[l];
+    }
+  }
+  const int A = towers[0].n_out;
+  std::vector<float> xb(D);
+  for (int e = 0; e < n; ++e) {
+    for (int k = 0; k < D; ++k) xb[k] = bf16_round(obs[(size_t)e * D + k]);
+    float l[8], v;
+    tower_forward_bf16(towers[0], wb[0], D, activation, xb.data(), l);
+    if (n_towers == 2) {
+      tower_forward_bf16(towers[1], wb[1], D, activation, xb.data(), &v);
+      if (head1) head1[e] = v;
+    }
+    if (head0) std::memcpy(head0 + (size_t)e * A, l, sizeof(float) * A);
+    actions[e] = mode == PE_POLICY_ARGMAX ? policy_argmax(l, A)
+                                          : policy_sample(l, A, policy_uniform(seed, env_id_offset + (uint32_t)e, t));
+  }
+  return PE_OK;
+}
 
 int pe_policy_forward_host(int32_t n, int32_t D, int32_t n_towers, const pe_policy_tower* towers,
                            int32_t activation, const float* obs, int32_t mode, uint64_t seed,

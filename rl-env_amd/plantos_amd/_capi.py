@@ -53,11 +53,13 @@ EXPORTS = [
     "pe_policy_forward_rows",
     "pe_replay_select", "pe_replay_select_host", "pe_replay_store", "pe_replay_sample",
     "pe_replay_sample_indices_host", "pe_replay_target", "pe_replay_target_host",
+    "pe_policy_create_prec", "pe_policy_precision", "pe_policy_forward_host_bf16",
 ]
 PE_REPLAY_CTRL_WORDS = 4
 PE_RC_STEPS, PE_RC_DRAWS = 0, 1
 PE_ACT_TANH, PE_ACT_RELU = 0, 1
 PE_POLICY_ARGMAX, PE_POLICY_SAMPLE = 0, 1
+PE_PREC_F32, PE_PREC_BF16 = 0, 1
 
 
 class PEConfig(ctypes.Structure):
@@ -159,6 +161,11 @@ def lib():
         L.pe_internal_policy_plan.argtypes = [I32, I32, I32, I32, ctypes.POINTER(PEPolicyLstm),
                                               ctypes.POINTER(PEPolicyTower), I32, I32, ctypes.POINTER(PEPolicyPlanInfo)]
         L.pe_internal_policy_plan.restype = ctypes.c_int
+    if hasattr(L, "pe_internal_policy_plan_prec"):
+        L.pe_internal_policy_plan_prec.argtypes = [I32, I32, I32, I32, ctypes.POINTER(PEPolicyLstm),
+                                                   ctypes.POINTER(PEPolicyTower), I32, I32, I32,
+                                                   ctypes.POINTER(PEPolicyPlanInfo)]
+        L.pe_internal_policy_plan_prec.restype = ctypes.c_int
     L.pe_last_error.argtypes = []
     L.pe_last_error.restype = ctypes.c_char_p
     D = ctypes.c_double
@@ -222,6 +229,14 @@ def lib():
         L.pe_replay_sample_indices_host.argtypes = [I32, I32, I32, U64, U64, U64, P]
         L.pe_replay_target.argtypes = [I32, I32, P, P, P, D, P, P]
         L.pe_replay_target_host.argtypes = [I32, I32, P, P, P, D, P]
+    if hasattr(L, "pe_policy_create_prec"):  # (an older library loaded for a same-box A/B lacks them)
+        TP = ctypes.POINTER(PEPolicyTower)
+        L.pe_policy_create_prec.argtypes = [P, I32, TP, I32, I32, I32, ctypes.POINTER(P)]
+        L.pe_policy_create_prec.restype = ctypes.c_int
+        L.pe_policy_precision.argtypes = [P]
+        L.pe_policy_precision.restype = I32
+        L.pe_policy_forward_host_bf16.argtypes = [I32, I32, I32, TP, I32, P, I32, U64, U32, U32, P, P, P]
+        L.pe_policy_forward_host_bf16.restype = ctypes.c_int
     for name in ("pe_policy_forward_rows", "pe_replay_select", "pe_replay_select_host", "pe_replay_store",
                  "pe_replay_sample", "pe_replay_sample_indices_host", "pe_replay_target", "pe_replay_target_host",
                  "pe_policy_value", "pe_policy_value_lstm", "pe_logf_host", "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
@@ -258,12 +273,18 @@ def plan(cfg, n_envs, num_cus):
     return info
 
 
-def policy_plan(obs_dim, n_envs, num_cus, lstms, shapes, activation, env_tile=0):
+def policy_plan(obs_dim, n_envs, num_cus, lstms, shapes, activation, env_tile=0, precision=None):
     """pe_internal_policy_plan: the env tile, LDS and buffer sizes pe_policy_create (lstms None) or
     pe_policy_create_lstm would choose for obs rows of `obs_dim` values, `n_envs` envs and a device of
-    `num_cus` CUs.  lstms / shapes: PEPolicyLstm / PEPolicyTower arrays.  Needs no device; raises as
-    the create call does."""
+    `num_cus` CUs.  lstms / shapes: PEPolicyLstm / PEPolicyTower arrays.  precision: None, or a
+    PE_PREC_* for pe_internal_policy_plan_prec (what pe_policy_create_prec would choose).  Needs no
+    device; raises as the create call does."""
     info = PEPolicyPlanInfo()
+    if precision is not None:
+        check(lib().pe_internal_policy_plan_prec(int(obs_dim), int(n_envs), int(num_cus), len(shapes), lstms, shapes,
+                                                 int(activation), int(env_tile), int(precision), ctypes.byref(info)),
+              "pe_policy_create_prec" if lstms is None else "pe_policy_create_lstm")
+        return info
     check(lib().pe_internal_policy_plan(int(obs_dim), int(n_envs), int(num_cus), len(shapes), lstms, shapes,
                                         int(activation), int(env_tile), ctypes.byref(info)),
           "pe_policy_create" if lstms is None else "pe_policy_create_lstm")

@@ -32,6 +32,7 @@ import numpy as np
 from . import _capi as C
 
 ACTIVATIONS = {"tanh": C.PE_ACT_TANH, "relu": C.PE_ACT_RELU}
+PRECISIONS = {"f32": C.PE_PREC_F32, "bf16": C.PE_PREC_BF16}
 
 
 def check_towers(towers):
@@ -136,12 +137,15 @@ def _check_tensor_shapes(towers, tensors, obs_dim):
             k = t[l]
 
 
-def host_forward(towers, tensors, activation, obs, deterministic=True, seed=0, env_id_offset=0, t=0):
-    """The host twin (pe_policy_forward_host): the definition of the policy's outputs in plain
-    C++, no device.  obs f32 [n, D] (numpy); tensors as parse_state_dict returns them (torch
-    CPU tensors or numpy).  Returns (actions i32 [n], logits f32 [n, A], values f32 [n] or
-    None) as numpy arrays."""
+def host_forward(towers, tensors, activation, obs, deterministic=True, seed=0, env_id_offset=0, t=0,
+                 precision="f32"):
+    """The host twin (pe_policy_forward_host; pe_policy_forward_host_bf16 for precision "bf16"):
+    the definition of the policy's outputs in plain C++, no device.  obs f32 [n, D] (numpy);
+    tensors as parse_state_dict returns them (torch CPU tensors or numpy).  Returns (actions
+    i32 [n], logits f32 [n, A], values f32 [n] or None) as numpy arrays."""
     towers = check_towers(towers)
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
     if activation not in ACTIVATIONS:
         raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
     obs = np.ascontiguousarray(obs, np.float32)
@@ -158,7 +162,8 @@ def host_forward(towers, tensors, activation, obs, deterministic=True, seed=0, e
     logits = np.zeros((n, A), np.float32)
     values = np.zeros(n, np.float32) if len(towers) == 2 else None
     P = ctypes.c_void_p
-    C.check(C.lib().pe_policy_forward_host(
+    twin = C.lib().pe_policy_forward_host_bf16 if precision == "bf16" else C.lib().pe_policy_forward_host
+    C.check(twin(
         n, D, len(towers), arr, ACTIVATIONS[activation], obs.ctypes.data_as(P),
         C.PE_POLICY_ARGMAX if deterministic else C.PE_POLICY_SAMPLE, int(seed) & 0xFFFFFFFFFFFFFFFF,
         int(env_id_offset) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, actions.ctypes.data_as(P), logits.ctypes.data_as(P),
@@ -321,16 +326,28 @@ class Policy(_PolicyBase):
     towers: [[h1, .., A], [h1, .., 1]] (pi and vf nets) or [[h1, .., A]] (a Q-network);
     activation "tanh" or "relu"; seed keys the action sampler (deterministic=False);
     env_tile (32 / 64, None = the library's choice) is the kernel's envs per workgroup: it
-    changes speed, never results.  Weights start at zero: `load` them.  Close the policy
-    before its batch."""
+    changes speed, never results.  precision "f32" (the default) or "bf16": bf16 rounds the
+    obs, the hidden weights and the hidden activations to bf16 and accumulates in f32 on the
+    bf16 MFMA (include/plantos_batch.h, "Reduced-precision policy inference"; `host_forward`
+    is then the bf16 twin); biases, heads and outputs stay f32.  Weights start at zero: `load`
+    them.  Close the policy before its batch."""
 
     def __init__(self, batch_or_venv, towers=((256, 256, 5), (256, 256, 1)), activation="tanh", seed=0,
-                 env_tile=None):
+                 env_tile=None, precision="f32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
+        self._precision = precision
         super().__init__(batch_or_venv, towers, activation, seed, env_tile)
 
     def _create(self, env_tile, out):
-        C.check(C.lib().pe_policy_create(self.batch.handle, len(self.towers), _tower_structs(self.towers),
-                                         ACTIVATIONS[self.activation], env_tile, out), "pe_policy_create")
+        C.check(C.lib().pe_policy_create_prec(self.batch.handle, len(self.towers), _tower_structs(self.towers),
+                                              ACTIVATIONS[self.activation], env_tile, PRECISIONS[self._precision], out),
+                "pe_policy_create")
+
+    @property
+    def precision(self):
+        """"f32" or "bf16", as given to the constructor."""
+        return self._precision
 
     @classmethod
     def from_state_dict(cls, env, sd, activation=None, **kw):
@@ -433,7 +450,8 @@ class Policy(_PolicyBase):
         if tensors is None:
             raise ValueError("no weights loaded")
         return host_forward(self.towers, tensors, self.activation, obs_np, deterministic=deterministic,
-                            seed=self.seed, env_id_offset=int(self.batch.cfg.env_id_offset), t=t)
+                            seed=self.seed, env_id_offset=int(self.batch.cfg.env_id_offset), t=t,
+                            precision=self._precision)
 
 
 # ------------------------------------------------------------------ recurrent policy

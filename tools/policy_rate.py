@@ -29,6 +29,15 @@ their medians and spread (max - min).
 
   python tools/policy_rate.py --host-cost --label new --out profiles/policy_host_cost.json
   python tools/policy_rate.py --host-cost --label parent --package-root <parent>/rl-env_amd --out ...
+
+--precision bf16 measures Policy(precision="bf16") against the f32 policy: the same run and the same
+method (warm-up, `rounds` windows of `iters` calls, device events, median / min / max), the headline
+geometry with codes, both nets, 65536 and 4096 envs, the f32 kernel and the bf16 kernel alternating
+-- the order swaps from round to round --, and the worst difference of the two kernels' heads.  Then
+one RolloutCollector step (collect() of 5 steps / 5, A2C's net) with each precision, alternating the
+same way.
+
+  python tools/policy_rate.py --precision bf16 --out profiles/policy_rate_bf16.json
 """
 import argparse
 import ctypes
@@ -116,8 +125,100 @@ def host_cost_main(args):
         f.write(json.dumps(doc, indent=1) + "\n")
 
 
+def spread(v):
+    med = statistics.median(v)
+    return {"us_median": round(med * 1e6, 2), "us_min": round(min(v) * 1e6, 2), "us_max": round(max(v) * 1e6, 2)}
+
+
+def outside_both_spreads(lo, hi):
+    """whether every window of `lo` is below every window of `hi`"""
+    return lo["us_max"] < hi["us_min"]
+
+
+def bf16_main(args):
+    import torch
+    from plantos_amd import PlantOSBatch, Policy, RolloutCollector
+    from plantos_amd import _capi as C
+    L, dev, P = C.lib(), "cuda:0", ctypes.c_void_p
+    res = {"tool": "policy_rate --precision bf16", "device": torch.cuda.get_device_name(0), "geometry": GEOMETRY,
+           "steps_before": args.steps, "iters": args.iters, "rounds": args.rounds, "cases": [], "rollout": []}
+    precisions = ("f32", "bf16")
+    for n in args.envs:
+        b = PlantOSBatch(n, seed=7, device=dev, obs_codes=True, **GEOMETRY)
+        D = b.obs_dim
+        act = torch.empty(n, dtype=torch.int32, device=dev)
+        for t in range(args.steps):
+            b.synth_actions(7, t, out=act)
+            b.step(act)
+        codes = b.obs.clone()
+        for name, (towers, actv) in NETS.items():
+            torch.manual_seed(1)
+            tensors = []
+            for t in towers:
+                k, tw = D, []
+                for w in t:
+                    lin = torch.nn.Linear(k, w).to(dev)
+                    tw.append((lin.weight.detach(), lin.bias.detach()))
+                    k = w
+                tensors.append(tw)
+            pols = {pr: Policy(b, towers, actv, precision=pr).load(tensors) for pr in precisions}
+            stream, fwd, cp = b._stream(), L.pe_policy_forward, P(codes.data_ptr())
+
+            def path(pol):
+                tail = (0, 0, 0, P(pol.actions.data_ptr()), P(pol.logits.data_ptr()),
+                        P(pol.values.data_ptr()) if pol.values is not None else None, stream)
+                return lambda: fwd(pol._p, cp, 1, *tail)
+
+            paths = {pr: path(pols[pr]) for pr in precisions}
+            for fn in paths.values():
+                for _ in range(5):
+                    C.check(fn(), "pe_policy_forward")
+            torch.cuda.synchronize()
+            diff = float((pols["f32"].logits - pols["bf16"].logits).abs().max())
+            agree = float((pols["f32"].actions == pols["bf16"].actions).float().mean())
+            per = {pr: [] for pr in precisions}
+            for r in range(args.rounds):
+                for pr in (precisions if r % 2 == 0 else precisions[::-1]):
+                    per[pr].append(window(torch, paths[pr], args.iters))
+            macs = sum(kk * w for t in towers for kk, w in zip([D] + t[:-1], t))
+            case = {"envs": n, "net": name, "towers": towers, "activation": actv, "macs_per_env": macs,
+                    "env_tile": {pr: pols[pr].env_tile for pr in precisions},
+                    "worst_logit_difference": diff, "argmax_agreement": round(agree, 5)}
+            for pr in precisions:
+                case[pr] = spread(per[pr])
+                case[pr]["TFLOPs"] = round(2 * macs * n / statistics.median(per[pr]) / 1e12, 2)
+            case["f32_over_bf16"] = round(case["f32"]["us_median"] / case["bf16"]["us_median"], 3)
+            case["bf16_below_f32_outside_both_spreads"] = outside_both_spreads(case["bf16"], case["f32"])
+            res["cases"].append(case)
+            if name == "a2c":  # one collected step: collect() of 5 steps / 5
+                T = 5
+                cols = {pr: RolloutCollector(b, pols[pr], T) for pr in precisions}
+                for col in cols.values():
+                    for _ in range(3):
+                        col.collect()
+                torch.cuda.synchronize()
+                per = {pr: [] for pr in precisions}
+                for r in range(args.rounds):
+                    for pr in (precisions if r % 2 == 0 else precisions[::-1]):
+                        per[pr].append(window(torch, cols[pr].collect, max(args.iters // T, 1)) / T)
+                row = {"envs": n, "n_steps": T, "unit": "us per collected step"}
+                for pr in precisions:
+                    row[pr] = spread(per[pr])
+                row["f32_over_bf16"] = round(row["f32"]["us_median"] / row["bf16"]["us_median"], 3)
+                res["rollout"].append(row)
+            for pol in pols.values():
+                pol.close()
+        b.close()
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
     ap.add_argument("--host-cost", action="store_true")
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--label", default="new")
@@ -134,6 +235,8 @@ def main():
         raise SystemExit("policy_rate: no GPU (a time cannot be measured on a CPU)")
     if args.host_cost:
         return host_cost_main(args)
+    if args.precision == "bf16":
+        return bf16_main(args)
     from plantos_amd import PlantOSBatch, Policy
     from plantos_amd import _capi as C
     L = C.lib()
