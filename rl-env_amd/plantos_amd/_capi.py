@@ -32,29 +32,7 @@ def map_algo_id(name):
     'maze' selects the maze; anything else is 'original', as there."""
     return PE_MAP_MAZE if name == "maze" else PE_MAP_ORIGINAL
 
-# exported symbols (tests/test_capi_symbols.py checks they match include/plantos_batch.h)
-EXPORTS = [
-    "pe_default_config", "pe_obs_dim", "pe_create", "pe_destroy", "pe_seed", "pe_reset", "pe_step",
-    "pe_get_info", "pe_get_state", "pe_set_state", "pe_load_maps", "pe_synth_actions", "pe_poll_errors",
-    "pe_num_envs", "pe_kernel_variant", "pe_kernel_name", "pe_prefetch_every", "pe_state_bytes", "pe_last_error",
-    "pe_pystream_create", "pe_pystream_next", "pe_pystream_getrandbits32", "pe_pystream_destroy",
-    "pe_curriculum_enable", "pe_curriculum_disable", "pe_curriculum_get",
-    "pe_mcts_create", "pe_mcts_destroy", "pe_mcts_seed", "pe_mcts_set_rng", "pe_mcts_get_rng", "pe_mcts_search",
-    "pe_mcts_kernel_name",
-    "pe_step_codes", "pe_obs_code_table", "pe_expand_obs_codes",
-    "pe_render_tables", "pe_render",
-    "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward", "pe_policy_forward_host",
-    "pe_policy_math_host", "pe_policy_env_tile",
-    "pe_policy_create_lstm", "pe_policy_load_lstm", "pe_policy_forward_lstm", "pe_policy_lstm_reset_state",
-    "pe_policy_lstm_get_state", "pe_policy_lstm_set_state", "pe_policy_lstm_forward_host",
-    "pe_policy_value", "pe_policy_value_lstm",
-    "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
-    "pe_logf_host",
-    "pe_policy_forward_rows",
-    "pe_replay_select", "pe_replay_select_host", "pe_replay_store", "pe_replay_sample",
-    "pe_replay_sample_indices_host", "pe_replay_target", "pe_replay_target_host",
-    "pe_policy_create_prec", "pe_policy_precision", "pe_policy_forward_host_bf16",
-]
+
 PE_REPLAY_CTRL_WORDS = 4
 PE_RC_STEPS, PE_RC_DRAWS = 0, 1
 PE_ACT_TANH, PE_ACT_RELU = 0, 1
@@ -110,11 +88,108 @@ class PlantOSNativeError(RuntimeError):
     pass
 
 
+def _signatures():
+    P, I32, U32, I64, U64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64
+    INT, F, D, STR = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_char_p
+    CP, TP, LP, PP = (ctypes.POINTER(t) for t in (PEConfig, PEPolicyTower, PEPolicyLstm, P))
+    step = [P, P, I32] + [P] * 9
+    forward_host = [I32, I32, I32, TP, I32, P, I32, U64, U32, U32, P, P, P]
+    record = [I32, I32] + [P] * 8 + [D] + [P] * 6
+    gae = [I32, I32, I64, I64, I64, I64, P, P, P, P, D, D, P, P]
+    abi = {  # in the header's order
+        "pe_default_config": (None, [CP, I32, I32, I32, I32, I32]),
+        "pe_obs_dim": (I32, [CP]),
+        "pe_create": (INT, [CP, I32, I32, PP]),
+        "pe_destroy": (INT, [P]),
+        "pe_seed": (INT, [P, U64, I32, P]),
+        "pe_reset": (INT, [P, P, P, P]),
+        "pe_step": (INT, step),
+        "pe_step_codes": (INT, step),
+        "pe_obs_code_table": (INT, [P, P]),
+        "pe_expand_obs_codes": (INT, [P, I32, I32, P, I64, P, P, P, P, P]),
+        "pe_get_info": (INT, [P, P, P]),
+        "pe_get_state": (INT, [P] * 6),
+        "pe_set_state": (INT, [P] * 6),
+        "pe_load_maps": (INT, [P, I32, P, P, P, P, P]),
+        "pe_synth_actions": (INT, [P, U64, U32, P, P]),
+        "pe_poll_errors": (INT, [P, ctypes.POINTER(I32), P]),
+        "pe_curriculum_enable": (INT, [P, D, D, D, I32, I32, P]),
+        "pe_curriculum_disable": (INT, [P]),
+        "pe_curriculum_get": (INT, [P, P, P, P]),
+        "pe_pystream_create": (INT, [CP, I64, PP]),
+        "pe_pystream_next": (INT, [P, I32, P, P]),
+        "pe_pystream_getrandbits32": (U32, [P]),
+        "pe_pystream_destroy": (INT, [P]),
+        "pe_mcts_create": (INT, [P, I32, D, I32, PP]),
+        "pe_mcts_destroy": (INT, [P]),
+        "pe_mcts_seed": (INT, [P, P, U32, P]),
+        "pe_mcts_set_rng": (INT, [P, P, P]),
+        "pe_mcts_get_rng": (INT, [P, P, P]),
+        "pe_mcts_search": (INT, [P] * 7),
+        "pe_mcts_kernel_name": (INT, [P, ctypes.POINTER(STR)]),
+        "pe_render_tables": (INT, [CP, I32, P, P]),
+        "pe_render": (INT, [P, I32, P, I32, P, I64, I64, P]),
+        "pe_policy_create": (INT, [P, I32, TP, I32, I32, PP]),
+        "pe_policy_destroy": (INT, [P]),
+        "pe_policy_load": (INT, [P, TP, P]),
+        "pe_policy_forward": (INT, [P, P, I32, I32, U64, U32, P, P, P, P]),
+        "pe_policy_forward_rows": (INT, [P, I32, P, I32, P, P, P, P]),
+        "pe_policy_forward_host": (INT, forward_host),
+        "pe_policy_math_host": (INT, [I32, I32, P, P]),
+        "pe_policy_env_tile": (I32, [P]),
+        "pe_policy_create_lstm": (INT, [P, I32, LP, TP, I32, I32, PP]),
+        "pe_policy_load_lstm": (INT, [P, LP, TP, P]),
+        "pe_policy_forward_lstm": (INT, [P, P, I32, P, P, I32, U64, U32, P, P, P, P]),
+        "pe_policy_lstm_reset_state": (INT, [P, P]),
+        "pe_policy_lstm_get_state": (INT, [P, I32, P, P, P]),
+        "pe_policy_lstm_set_state": (INT, [P, I32, P, P, P]),
+        "pe_policy_lstm_forward_host": (INT, [I32, I32, I32, LP, TP, I32, P, P, P, P, I32, U64, U32, U32, P, P, P]),
+        "pe_policy_value": (INT, [P, P, I32, P, P, P, P]),
+        "pe_policy_value_lstm": (INT, [P, P, I32, P, P, P, P, P, P]),
+        "pe_policy_create_prec": (INT, [P, I32, TP, I32, I32, I32, PP]),
+        "pe_policy_precision": (I32, [P]),
+        "pe_policy_forward_host_bf16": (INT, forward_host),
+        "pe_rollout_record": (INT, record + [P]),
+        "pe_rollout_record_host": (INT, record),
+        "pe_logf_host": (INT, [I32, P, P]),
+        "pe_rollout_gae": (INT, gae + [P]),
+        "pe_rollout_gae_host": (INT, gae),
+        "pe_replay_select": (INT, [I32, I32, P, P, P, U64, U32, P, P, P]),
+        "pe_replay_select_host": (INT, [I32, I32, P, F, U64, U64, U32, P, P]),
+        "pe_replay_store": (INT, [I32] * 5 + [P] * 19),
+        "pe_replay_sample": (INT, [I32] * 4 + [P] * 5 + [U64] + [P] * 8),
+        "pe_replay_sample_indices_host": (INT, [I32, I32, I32, U64, U64, U64, P]),
+        "pe_replay_target": (INT, [I32, I32, P, P, P, D, P, P]),
+        "pe_replay_target_host": (INT, [I32, I32, P, P, P, D, P]),
+        "pe_num_envs": (I32, [P]),
+        "pe_kernel_variant": (I32, [P]),
+        "pe_kernel_name": (STR, [P]),
+        "pe_prefetch_every": (I32, [P]),
+        "pe_state_bytes": (U64, [P]),
+        "pe_last_error": (STR, []),
+    }
+    plan = [I32, I32, I32, I32, LP, TP, I32, I32]
+    internal = {
+        "pe_internal_plan": (INT, [CP, I32, I32, ctypes.POINTER(PEPlanInfo)]),
+        "pe_internal_policy_plan": (INT, plan + [ctypes.POINTER(PEPolicyPlanInfo)]),
+        "pe_internal_policy_plan_prec": (INT, plan + [I32, ctypes.POINTER(PEPolicyPlanInfo)]),
+    }
+    return abi, internal
+
+
+# name -> (restype, [argtypes]).  SIGNATURES: every function of include/plantos_batch.h
+# (tests/test_capi_symbols.py checks each entry against the header's prototype);
+# INTERNAL_SIGNATURES: the plan entry points of csrc/pe_handle.hpp, which are not part of the ABI.
+SIGNATURES, INTERNAL_SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
 def lib():
-    """Load libplantos_hip.so (built by rl-env_amd/build.py); raise if absent."""
+    """Load libplantos_hip.so (built by rl-env_amd/build.py); raise if absent.  A function the
+    loaded library lacks (an older build given through PLANTOS_HIP_LIB) stays unbound: using it
+    raises AttributeError."""
     global _lib
     if _lib is not None:
         return _lib
@@ -123,134 +198,10 @@ def lib():
             f"{LIB_PATH} not found: build it with `python rl-env_amd/build.py` "
             "(there is no CPU fallback for the PlantOS hot path)")
     L = ctypes.CDLL(LIB_PATH)
-    P, I32, U64, U32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint32
-    CP = ctypes.POINTER(PEConfig)
-    L.pe_default_config.argtypes = [CP, I32, I32, I32, I32, I32]
-    L.pe_default_config.restype = None
-    L.pe_obs_dim.argtypes = [CP]
-    L.pe_obs_dim.restype = I32
-    L.pe_create.argtypes = [CP, I32, I32, ctypes.POINTER(P)]
-    L.pe_destroy.argtypes = [P]
-    L.pe_seed.argtypes = [P, U64, I32, P]
-    L.pe_reset.argtypes = [P, P, P, P]
-    L.pe_step.argtypes = [P, P, I32, P, P, P, P, P, P, P, P, P]
-    if hasattr(L, "pe_step_codes"):  # (ABI 4; an older library loaded for a same-box A/B lacks them)
-        L.pe_step_codes.argtypes = [P, P, I32, P, P, P, P, P, P, P, P, P]
-        L.pe_obs_code_table.argtypes = [P, P]
-        L.pe_expand_obs_codes.argtypes = [P, I32, I32, P, ctypes.c_int64, P, P, P, P, P]
-    L.pe_get_info.argtypes = [P, P, P]
-    L.pe_get_state.argtypes = [P, P, P, P, P, P]
-    L.pe_set_state.argtypes = [P, P, P, P, P, P]
-    L.pe_load_maps.argtypes = [P, I32, P, P, P, P, P]
-    L.pe_synth_actions.argtypes = [P, U64, U32, P, P]
-    L.pe_poll_errors.argtypes = [P, ctypes.POINTER(I32), P]
-    L.pe_num_envs.argtypes = [P]
-    L.pe_num_envs.restype = I32
-    L.pe_kernel_variant.argtypes = [P]
-    L.pe_kernel_variant.restype = I32
-    L.pe_kernel_name.argtypes = [P]
-    L.pe_prefetch_every.argtypes = [P]
-    L.pe_prefetch_every.restype = I32
-    L.pe_kernel_name.restype = ctypes.c_char_p
-    L.pe_state_bytes.argtypes = [P]
-    L.pe_state_bytes.restype = U64
-    if hasattr(L, "pe_internal_plan"):  # (not part of the ABI: csrc/pe_handle.hpp)
-        L.pe_internal_plan.argtypes = [CP, I32, I32, ctypes.POINTER(PEPlanInfo)]
-        L.pe_internal_plan.restype = ctypes.c_int
-    if hasattr(L, "pe_internal_policy_plan"):  # (not part of the ABI: csrc/pe_handle.hpp)
-        L.pe_internal_policy_plan.argtypes = [I32, I32, I32, I32, ctypes.POINTER(PEPolicyLstm),
-                                              ctypes.POINTER(PEPolicyTower), I32, I32, ctypes.POINTER(PEPolicyPlanInfo)]
-        L.pe_internal_policy_plan.restype = ctypes.c_int
-    if hasattr(L, "pe_internal_policy_plan_prec"):
-        L.pe_internal_policy_plan_prec.argtypes = [I32, I32, I32, I32, ctypes.POINTER(PEPolicyLstm),
-                                                   ctypes.POINTER(PEPolicyTower), I32, I32, I32,
-                                                   ctypes.POINTER(PEPolicyPlanInfo)]
-        L.pe_internal_policy_plan_prec.restype = ctypes.c_int
-    L.pe_last_error.argtypes = []
-    L.pe_last_error.restype = ctypes.c_char_p
-    D = ctypes.c_double
-    L.pe_curriculum_enable.argtypes = [P, D, D, D, I32, I32, P]
-    L.pe_curriculum_disable.argtypes = [P]
-    L.pe_curriculum_get.argtypes = [P, P, P, P]
-    L.pe_pystream_create.argtypes = [CP, ctypes.c_int64, ctypes.POINTER(P)]
-    L.pe_pystream_next.argtypes = [P, I32, P, P]
-    L.pe_pystream_getrandbits32.argtypes = [P]
-    L.pe_pystream_getrandbits32.restype = U32
-    L.pe_pystream_destroy.argtypes = [P]
-    L.pe_mcts_create.argtypes = [P, I32, D, I32, ctypes.POINTER(P)]
-    L.pe_mcts_destroy.argtypes = [P]
-    L.pe_mcts_seed.argtypes = [P, P, U32, P]
-    L.pe_mcts_set_rng.argtypes = [P, P, P]
-    L.pe_mcts_get_rng.argtypes = [P, P, P]
-    L.pe_mcts_search.argtypes = [P, P, P, P, P, P, P]
-    L.pe_mcts_kernel_name.argtypes = [P, ctypes.POINTER(ctypes.c_char_p)]
-    L.pe_mcts_kernel_name.restype = ctypes.c_int
-    if hasattr(L, "pe_render"):  # (an older library loaded for a same-box A/B lacks them)
-        L.pe_render_tables.argtypes = [CP, I32, P, P]
-        L.pe_render.argtypes = [P, I32, P, I32, P, ctypes.c_int64, ctypes.c_int64, P]
-    if hasattr(L, "pe_policy_create"):  # (an older library loaded for a same-box A/B lacks them)
-        TP = ctypes.POINTER(PEPolicyTower)
-        L.pe_policy_create.argtypes = [P, I32, TP, I32, I32, ctypes.POINTER(P)]
-        L.pe_policy_destroy.argtypes = [P]
-        L.pe_policy_load.argtypes = [P, TP, P]
-        L.pe_policy_forward.argtypes = [P, P, I32, I32, U64, U32, P, P, P, P]
-        L.pe_policy_forward_host.argtypes = [I32, I32, I32, TP, I32, P, I32, U64, U32, U32, P, P, P]
-        L.pe_policy_math_host.argtypes = [I32, I32, P, P]
-        L.pe_policy_env_tile.argtypes = [P]
-        L.pe_policy_env_tile.restype = I32
-    if hasattr(L, "pe_policy_create_lstm"):  # (an older library loaded for a same-box A/B lacks them)
-        TP, LP = ctypes.POINTER(PEPolicyTower), ctypes.POINTER(PEPolicyLstm)
-        L.pe_policy_create_lstm.argtypes = [P, I32, LP, TP, I32, I32, ctypes.POINTER(P)]
-        L.pe_policy_load_lstm.argtypes = [P, LP, TP, P]
-        L.pe_policy_forward_lstm.argtypes = [P, P, I32, P, P, I32, U64, U32, P, P, P, P]
-        L.pe_policy_lstm_reset_state.argtypes = [P, P]
-        L.pe_policy_lstm_get_state.argtypes = [P, I32, P, P, P]
-        L.pe_policy_lstm_set_state.argtypes = [P, I32, P, P, P]
-        L.pe_policy_lstm_forward_host.argtypes = [I32, I32, I32, LP, TP, I32, P, P, P, P, I32, U64, U32, U32, P, P, P]
-    if hasattr(L, "pe_policy_value"):  # (an older library loaded for a same-box A/B lacks them)
-        L.pe_policy_value.argtypes = [P, P, I32, P, P, P, P]
-        L.pe_policy_value_lstm.argtypes = [P, P, I32, P, P, P, P, P, P]
-    if hasattr(L, "pe_rollout_record"):  # (an older library loaded for a same-box A/B lacks them)
-        I64 = ctypes.c_int64
-        rec = [I32, I32, P, P, P, P, P, P, P, P, D, P, P, P, P, P, P]
-        gae = [I32, I32, I64, I64, I64, I64, P, P, P, P, D, D, P, P]
-        L.pe_rollout_record.argtypes = rec + [P]
-        L.pe_rollout_record_host.argtypes = rec
-        L.pe_rollout_gae.argtypes = gae + [P]
-        L.pe_rollout_gae_host.argtypes = gae
-        L.pe_logf_host.argtypes = [I32, P, P]
-    if hasattr(L, "pe_replay_select"):  # (an older library loaded for a same-box A/B lacks them)
-        F = ctypes.c_float
-        L.pe_policy_forward_rows.argtypes = [P, I32, P, I32, P, P, P, P]
-        L.pe_replay_select.argtypes = [I32, I32, P, P, P, U64, U32, P, P, P]
-        L.pe_replay_select_host.argtypes = [I32, I32, P, F, U64, U64, U32, P, P]
-        L.pe_replay_store.argtypes = [I32, I32, I32, I32, I32] + [P] * 19
-        L.pe_replay_sample.argtypes = [I32, I32, I32, I32, P, P, P, P, P, U64, P, P, P, P, P, P, P, P]
-        L.pe_replay_sample_indices_host.argtypes = [I32, I32, I32, U64, U64, U64, P]
-        L.pe_replay_target.argtypes = [I32, I32, P, P, P, D, P, P]
-        L.pe_replay_target_host.argtypes = [I32, I32, P, P, P, D, P]
-    if hasattr(L, "pe_policy_create_prec"):  # (an older library loaded for a same-box A/B lacks them)
-        TP = ctypes.POINTER(PEPolicyTower)
-        L.pe_policy_create_prec.argtypes = [P, I32, TP, I32, I32, I32, ctypes.POINTER(P)]
-        L.pe_policy_create_prec.restype = ctypes.c_int
-        L.pe_policy_precision.argtypes = [P]
-        L.pe_policy_precision.restype = I32
-        L.pe_policy_forward_host_bf16.argtypes = [I32, I32, I32, TP, I32, P, I32, U64, U32, U32, P, P, P]
-        L.pe_policy_forward_host_bf16.restype = ctypes.c_int
-    for name in ("pe_policy_forward_rows", "pe_replay_select", "pe_replay_select_host", "pe_replay_store",
-                 "pe_replay_sample", "pe_replay_sample_indices_host", "pe_replay_target", "pe_replay_target_host",
-                 "pe_policy_value", "pe_policy_value_lstm", "pe_logf_host", "pe_rollout_record", "pe_rollout_record_host", "pe_rollout_gae", "pe_rollout_gae_host",
-                 "pe_policy_create_lstm", "pe_policy_load_lstm", "pe_policy_forward_lstm",
-                 "pe_policy_lstm_reset_state", "pe_policy_lstm_get_state", "pe_policy_lstm_set_state",
-                 "pe_policy_lstm_forward_host", "pe_policy_create", "pe_policy_destroy", "pe_policy_load", "pe_policy_forward",
-                 "pe_policy_forward_host", "pe_policy_math_host", "pe_create", "pe_destroy", "pe_seed", "pe_reset", "pe_step", "pe_get_info", "pe_get_state",
-                 "pe_set_state", "pe_load_maps", "pe_synth_actions", "pe_poll_errors", "pe_pystream_create",
-                 "pe_pystream_next", "pe_pystream_destroy", "pe_curriculum_enable", "pe_curriculum_disable",
-                 "pe_curriculum_get", "pe_mcts_create", "pe_mcts_destroy", "pe_mcts_seed", "pe_mcts_set_rng",
-                 "pe_mcts_get_rng", "pe_mcts_search", "pe_step_codes", "pe_obs_code_table",
-                 "pe_expand_obs_codes", "pe_render_tables", "pe_render"):
-        if hasattr(L, name):
-            getattr(L, name).restype = ctypes.c_int
+    for name, (restype, argtypes) in {**SIGNATURES, **INTERNAL_SIGNATURES}.items():
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -263,6 +214,33 @@ def check(rc, what):
         if rc == PE_ERR_NOROOM:
             raise ValueError(f"{what}: {msg}")
         raise PlantOSNativeError(f"{what} failed ({rc}): {msg}")
+
+
+def ptr(x):
+    """The data pointer of a numpy array or a torch tensor as a c_void_p; None for None."""
+    if x is None:
+        return None
+    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
+
+
+def stream_ptr(device):
+    """torch's current stream on `device` (a torch.device or an index) as a c_void_p."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+_TENSOR = None  # torch.Tensor, once torch is in use (this module imports without it)
+
+
+def on_device(x, dev_index, dtypes, shape=None):
+    """Whether x is a plain torch tensor on device `dev_index`, contiguous, of one of `dtypes` and
+    of `shape` (None: any shape)."""
+    global _TENSOR
+    if _TENSOR is None:
+        import torch
+        _TENSOR = torch.Tensor
+    return (type(x) is _TENSOR and x.is_cuda and x.get_device() == dev_index and x.is_contiguous()
+            and x.dtype in dtypes and (shape is None or tuple(x.shape) == shape))
 
 
 def plan(cfg, n_envs, num_cus):
@@ -318,8 +296,7 @@ class PyStream:
         np = self._np
         cells = np.zeros((k, self.G, self.G), np.uint8)
         rover = np.zeros((k, 2), np.int32)
-        check(lib().pe_pystream_next(self._h, int(k), cells.ctypes.data_as(ctypes.c_void_p),
-                                     rover.ctypes.data_as(ctypes.c_void_p)), "pe_pystream_next")
+        check(lib().pe_pystream_next(self._h, int(k), ptr(cells), ptr(rover)), "pe_pystream_next")
         return cells, rover
 
     def getrandbits32(self):

@@ -10,10 +10,6 @@ import torch
 from . import _capi as C
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class PlantOSBatch:
     """A batch of `num_envs` independent PlantOS envs on one GPU.
 
@@ -99,7 +95,7 @@ class PlantOSBatch:
 
     # ----------------------------------------------------------------- plumbing
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return C.stream_ptr(self.device)
 
     @property
     def handle(self):
@@ -139,7 +135,7 @@ class PlantOSBatch:
         """float32[256] (host): the value of every obs byte code (pe_obs_code_table)."""
         import numpy as np
         t = np.zeros(256, np.float32)
-        C.check(C.lib().pe_obs_code_table(self.handle, t.ctypes.data_as(ctypes.c_void_p)), "pe_obs_code_table")
+        C.check(C.lib().pe_obs_code_table(self.handle, C.ptr(t)), "pe_obs_code_table")
         return t
 
     def expand_codes(self, src, blocks=1, obs=None, reward=None, terminated=None, truncated=None):
@@ -162,12 +158,11 @@ class PlantOSBatch:
                                    ("truncated", truncated, torch.uint8, (rows,))):
             if t is None:
                 continue
-            if not (type(t) is torch.Tensor and t.dtype is dt and t.is_cuda and t.get_device() == self._dev_index
-                    and t.is_contiguous() and tuple(t.shape) == shape):
+            if not C.on_device(t, self._dev_index, (dt,), shape):
                 raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_expand_obs_codes(self.handle, int(blocks), n, _ptr(src), stride, _ptr(obs), _ptr(reward),
-                                                _ptr(terminated), _ptr(truncated), self._stream()),
+            C.check(C.lib().pe_expand_obs_codes(self.handle, int(blocks), n, C.ptr(src), stride, C.ptr(obs),
+                                                C.ptr(reward), C.ptr(terminated), C.ptr(truncated), self._stream()),
                     "pe_expand_obs_codes")
         return obs, reward, terminated, truncated
 
@@ -217,7 +212,7 @@ class PlantOSBatch:
         if mask is not None:
             m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_reset(self.handle, _ptr(m), _ptr(out), self._stream()), "pe_reset")
+            C.check(C.lib().pe_reset(self.handle, C.ptr(m), C.ptr(out), self._stream()), "pe_reset")
         return out
 
     def step(self, actions, obs=None, want_terminal_obs=True, io=None):
@@ -273,7 +268,7 @@ class PlantOSBatch:
     # ----------------------------------------------------------------- inspection
     def get_info(self):
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_get_info(self.handle, _ptr(self.info_buf), self._stream()), "pe_get_info")
+            C.check(C.lib().pe_get_info(self.handle, C.ptr(self.info_buf), self._stream()), "pe_get_info")
         return self.info_buf
 
     def get_state(self, parts=("cells", "visits", "explored", "scalars")):
@@ -286,7 +281,7 @@ class PlantOSBatch:
         explored = torch.empty((n, G, G), dtype=torch.int8, device=dev) if "explored" in parts else None
         scal = torch.empty((n, C.PE_NSCAL), dtype=torch.int32, device=dev) if "scalars" in parts else None
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_get_state(self.handle, _ptr(cells), _ptr(visits), _ptr(explored), _ptr(scal),
+            C.check(C.lib().pe_get_state(self.handle, C.ptr(cells), C.ptr(visits), C.ptr(explored), C.ptr(scal),
                                          self._stream()), "pe_get_state")
         out = {"cells": cells, "visits": visits, "explored": explored, "scalars": scal}
         return {k: v for k, v in out.items() if v is not None}
@@ -297,7 +292,7 @@ class PlantOSBatch:
         c, v, e, s = dev(cells, torch.uint8), dev(visits, torch.int32), dev(explored, torch.int8), dev(
             scalars, torch.int32)
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_set_state(self.handle, _ptr(c), _ptr(v), _ptr(e), _ptr(s), self._stream()),
+            C.check(C.lib().pe_set_state(self.handle, C.ptr(c), C.ptr(v), C.ptr(e), C.ptr(s), self._stream()),
                     "pe_set_state")
         torch.cuda.current_stream(self.device).synchronize()
 
@@ -309,7 +304,7 @@ class PlantOSBatch:
         k = idx.numel()
         out = torch.empty((k, self.obs_dim), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_load_maps(self.handle, k, _ptr(idx), _ptr(cl), _ptr(rv), _ptr(out), self._stream()),
+            C.check(C.lib().pe_load_maps(self.handle, k, C.ptr(idx), C.ptr(cl), C.ptr(rv), C.ptr(out), self._stream()),
                     "pe_load_maps")
         return out
 
@@ -354,14 +349,14 @@ class PlantOSBatch:
                              "contiguous pixels (strides (>= 3W, >= 3W, 3, 1))")
         self._idx_keep = idx  # alive until the launch has read it
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_render(self.handle, k, _ptr(idx), s, _ptr(out), out.stride(0) if k > 1 else 0,
+            C.check(C.lib().pe_render(self.handle, k, C.ptr(idx), s, C.ptr(out), out.stride(0) if k > 1 else 0,
                                       out.stride(1), self._stream()), "pe_render")
         return out
 
     def synth_actions(self, seed, t, out=None):
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device) if out is None else out
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_synth_actions(self.handle, int(seed), int(t), _ptr(out), self._stream()),
+            C.check(C.lib().pe_synth_actions(self.handle, int(seed), int(t), C.ptr(out), self._stream()),
                     "pe_synth_actions")
         return out
 
@@ -410,7 +405,7 @@ class PlantOSBatch:
         thr = torch.empty(self.num_envs, dtype=torch.float64, device=self.device)
         cnt = torch.empty((self.num_envs, 4), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            C.check(C.lib().pe_curriculum_get(self.handle, _ptr(thr), _ptr(cnt), self._stream()),
+            C.check(C.lib().pe_curriculum_get(self.handle, C.ptr(thr), C.ptr(cnt), self._stream()),
                     "pe_curriculum_get")
         return thr, cnt
 

@@ -37,17 +37,23 @@ def code_table(grid_size, lidar_range):
 
 def encode_obs(obs, grid_size, lidar_channels, lidar_range):
     """u8 codes of f32 obs rows [..., 5C+27] (column meaning as _get_lidar_obs lays
-    them out); expand(encode(x)) == x bit for bit for every obs the env produces."""
-    obs = np.asarray(obs, np.float32)
+    them out); expand(encode(x)) == x bit for bit for every obs the env produces.
+    A torch tensor gives a torch tensor on its device, anything else a numpy array.
+    The rule is pe_replay_math.hpp's replay_encode: products in f64, round-half-even."""
     C, R, G = int(lidar_channels), int(lidar_range), int(grid_size)
-    out = np.zeros(obs.shape, np.uint8)
-    lid = obs[..., :5 * C].reshape(obs.shape[:-1] + (C, 5))
-    o = out[..., :5 * C].reshape(out.shape[:-1] + (C, 5))
-    o[..., 0] = np.rint(lid[..., 0].astype(np.float64) * R).astype(np.uint8)        # distance r
-    o[..., 1:] = np.where(lid[..., 1:] != 0.0, R + 1, 0).astype(np.uint8)           # one-hot
-    out[..., :5 * C] = o.reshape(out[..., :5 * C].shape)
-    out[..., 5 * C:5 * C + 2] = (CODE_POS + np.rint(obs[..., 5 * C:5 * C + 2].astype(np.float64) * G)).astype(np.uint8)
-    out[..., 5 * C + 2:] = (CODE_VIS + np.rint(obs[..., 5 * C + 2:].astype(np.float64) * 10)).astype(np.uint8)
+    if hasattr(obs, "data_ptr"):  # a torch tensor
+        import torch as xp
+        x = obs.to(xp.float64)
+        out = xp.zeros(x.shape, dtype=xp.uint8, device=x.device)
+    else:
+        xp = np
+        x = np.asarray(obs, np.float32).astype(np.float64)
+        out = np.zeros(x.shape, np.uint8)
+    lidar, pos, vis = slice(0, 5 * C), slice(5 * C, 5 * C + 2), slice(5 * C + 2, None)
+    out[..., lidar] = xp.where(x[..., lidar] != 0, R + 1, 0)                        # one-hot
+    out[..., 0:5 * C:5] = xp.round(x[..., 0:5 * C:5] * R)                           # distance r
+    out[..., pos] = CODE_POS + xp.round(x[..., pos] * G)
+    out[..., vis] = CODE_VIS + xp.round(x[..., vis] * 10)
     return out
 
 

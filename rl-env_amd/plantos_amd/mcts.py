@@ -22,10 +22,6 @@ from . import _capi as C
 from .batch import PlantOSBatch
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class MCTS:
     def __init__(self, env, n_simulations=100, c_param=1.414, max_depth=50, seed=0):
         self.batch = env if isinstance(env, PlantOSBatch) else env.batch
@@ -54,7 +50,7 @@ class MCTS:
         return name.value.decode()
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.batch.device).cuda_stream)
+        return C.stream_ptr(self.batch.device)
 
     def seed(self, seed=0):
         """np.random.seed(...) per env: an int gives env e the seed `seed + e`; a
@@ -65,21 +61,18 @@ class MCTS:
             s = np.ascontiguousarray(seed, np.uint32)
             if s.shape != (self.num_envs,):
                 raise ValueError(f"expected {self.num_envs} seeds")
-            C.check(C.lib().pe_mcts_seed(self._h, s.ctypes.data_as(ctypes.c_void_p), 0, self._stream()),
-                    "pe_mcts_seed")
+            C.check(C.lib().pe_mcts_seed(self._h, C.ptr(s), 0, self._stream()), "pe_mcts_seed")
 
     def set_rng_state(self, key, pos):
         """key uint32 [N, 624], pos int [N]: numpy's get_state()[1], [2] per env."""
         key = np.ascontiguousarray(key, np.uint32).reshape(self.num_envs, 624)
         pos = np.ascontiguousarray(pos, np.int32).reshape(self.num_envs)
-        C.check(C.lib().pe_mcts_set_rng(self._h, key.ctypes.data_as(ctypes.c_void_p),
-                                        pos.ctypes.data_as(ctypes.c_void_p)), "pe_mcts_set_rng")
+        C.check(C.lib().pe_mcts_set_rng(self._h, C.ptr(key), C.ptr(pos)), "pe_mcts_set_rng")
 
     def get_rng_state(self):
         key = np.zeros((self.num_envs, 624), np.uint32)
         pos = np.zeros(self.num_envs, np.int32)
-        C.check(C.lib().pe_mcts_get_rng(self._h, key.ctypes.data_as(ctypes.c_void_p),
-                                        pos.ctypes.data_as(ctypes.c_void_p)), "pe_mcts_get_rng")
+        C.check(C.lib().pe_mcts_get_rng(self._h, C.ptr(key), C.ptr(pos)), "pe_mcts_get_rng")
         return key, pos
 
     def search(self, initial_state=None, mask=None, root_stats=False):
@@ -91,8 +84,8 @@ class MCTS:
         if mask is not None:
             m = torch.as_tensor(mask, device=self.batch.device).to(torch.uint8).contiguous()
         rs = (self.root_order, self.root_visits, self.root_value) if root_stats else (None, None, None)
-        C.check(C.lib().pe_mcts_search(self._h, _vp(m), _vp(self.actions), _vp(rs[0]), _vp(rs[1]), _vp(rs[2]),
-                                       self._stream()), "pe_mcts_search")
+        C.check(C.lib().pe_mcts_search(self._h, C.ptr(m), C.ptr(self.actions), *(C.ptr(x) for x in rs), self._stream()),
+                "pe_mcts_search")
         if root_stats:
             return self.actions, self.root_order, self.root_visits, self.root_value
         return self.actions

@@ -30,6 +30,7 @@ import re
 import numpy as np
 
 from . import _capi as C
+from ._capi import on_device
 
 ACTIVATIONS = {"tanh": C.PE_ACT_TANH, "relu": C.PE_ACT_RELU}
 PRECISIONS = {"f32": C.PE_PREC_F32, "bf16": C.PE_PREC_BF16}
@@ -116,8 +117,7 @@ def _tower_structs(towers, tensors=None, keep=None):
         if len(tensors[i]) != len(t):
             raise ValueError(f"tower {i}: expected {len(t)} (weight, bias) pairs, got {len(tensors[i])}")
         for l, (w, b) in enumerate(tensors[i]):
-            arr[i].weight[l] = w.ctypes.data if isinstance(w, np.ndarray) else w.data_ptr()
-            arr[i].bias[l] = b.ctypes.data if isinstance(b, np.ndarray) else b.data_ptr()
+            arr[i].weight[l], arr[i].bias[l] = C.ptr(w), C.ptr(b)
             if keep is not None:
                 keep += [w, b]
     return arr
@@ -161,13 +161,12 @@ def host_forward(towers, tensors, activation, obs, deterministic=True, seed=0, e
     actions = np.zeros(n, np.int32)
     logits = np.zeros((n, A), np.float32)
     values = np.zeros(n, np.float32) if len(towers) == 2 else None
-    P = ctypes.c_void_p
     twin = C.lib().pe_policy_forward_host_bf16 if precision == "bf16" else C.lib().pe_policy_forward_host
     C.check(twin(
-        n, D, len(towers), arr, ACTIVATIONS[activation], obs.ctypes.data_as(P),
+        n, D, len(towers), arr, ACTIVATIONS[activation], C.ptr(obs),
         C.PE_POLICY_ARGMAX if deterministic else C.PE_POLICY_SAMPLE, int(seed) & 0xFFFFFFFFFFFFFFFF,
-        int(env_id_offset) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, actions.ctypes.data_as(P), logits.ctypes.data_as(P),
-        values.ctypes.data_as(P) if values is not None else None), "pe_policy_forward_host")
+        int(env_id_offset) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, C.ptr(actions), C.ptr(logits), C.ptr(values)),
+        "pe_policy_forward_host")
     return actions, logits, values
 
 
@@ -176,12 +175,11 @@ def math_host(which, x):
     array, as the twins and the kernels compute them."""
     x = np.ascontiguousarray(x, np.float32)
     y = np.empty_like(x)
-    P = ctypes.c_void_p
     if which == "log":  # (a function of its own: pe_policy_math_host's selectors stay 0..2)
-        C.check(C.lib().pe_logf_host(x.size, x.ctypes.data_as(P), y.ctypes.data_as(P)), "pe_logf_host")
+        C.check(C.lib().pe_logf_host(x.size, C.ptr(x), C.ptr(y)), "pe_logf_host")
         return y
-    C.check(C.lib().pe_policy_math_host({"tanh": 0, "exp": 1, "sigmoid": 2}[which], x.size, x.ctypes.data_as(P),
-                                        y.ctypes.data_as(P)), "pe_policy_math_host")
+    C.check(C.lib().pe_policy_math_host({"tanh": 0, "exp": 1, "sigmoid": 2}[which], x.size, C.ptr(x), C.ptr(y)),
+            "pe_policy_math_host")
     return y
 
 
@@ -189,18 +187,10 @@ def _np(x):
     return x if isinstance(x, np.ndarray) else x.detach().cpu().numpy()
 
 
-_TENSOR = None  # torch.Tensor, once torch is in use (this module imports without it)
-
-
-def _on_dev(x, batch, dtypes, shape):
-    """Whether x is a plain torch tensor on the batch's device, contiguous, of one of `dtypes` and
-    of `shape` (None: any shape)."""
-    global _TENSOR
-    if _TENSOR is None:
-        import torch
-        _TENSOR = torch.Tensor
-    return (type(x) is _TENSOR and x.is_cuda and x.get_device() == batch._dev_index and x.is_contiguous()
-            and x.dtype in dtypes and (shape is None or tuple(x.shape) == shape))
+def _to_dev_f32(x, device):
+    """x as a contiguous float32 tensor on `device` (one that already is one is returned as it is)."""
+    import torch
+    return torch.as_tensor(x).detach().to(device=device, dtype=torch.float32).contiguous()
 
 
 class _PolicyBase:
@@ -237,7 +227,7 @@ class _PolicyBase:
             raise ValueError(f"{type(self).__name__} is closed")
         return self._p
 
-    def _stream(self):
+    def _stream(self):  # (C.stream_ptr's value as a plain int: every act / value call passes through here)
         return self._torch.cuda.current_stream(self.batch._dev_index).cuda_stream
 
     def close(self):
@@ -258,7 +248,7 @@ class _PolicyBase:
         n, D = b.num_envs, b.obs_dim
         if obs is None and not any_rows:
             obs = b.obs
-        if not (_on_dev(obs, b, (torch.float32, torch.uint8), None if any_rows else (n, D))
+        if not (on_device(obs, b._dev_index, (torch.float32, torch.uint8), None if any_rows else (n, D))
                 and (not any_rows or (obs.dim() == 2 and obs.shape[0] >= 1 and obs.shape[1] == D))):
             shape = f"(rows >= 1, {D})" if any_rows else (n, D)
             raise ValueError(f"obs must be a contiguous float32 or uint8 tensor of shape {shape} on {b.device}")
@@ -276,7 +266,7 @@ class _PolicyBase:
                                    ("values", v, torch.float32, (rows,))):
             if x is None and name != "actions":
                 continue  # an output not asked for
-            if not _on_dev(x, b, (dt,), shape):
+            if not on_device(x, b._dev_index, (dt,), shape):
                 raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {b.device}")
         if v is not None and len(self.towers) < 2:
             raise ValueError("a one-tower policy has no values")
@@ -295,7 +285,7 @@ class _PolicyBase:
         torch, b = self._torch, self.batch
         if x is None:
             return None
-        if not _on_dev(x, b, (torch.uint8, torch.bool), (b.num_envs,)):
+        if not on_device(x, b._dev_index, (torch.uint8, torch.bool), (b.num_envs,)):
             raise ValueError(f"{name} must be a contiguous uint8 or bool tensor of shape {(b.num_envs,)} on {b.device}")
         return x.data_ptr()
 
@@ -315,7 +305,7 @@ class _PolicyBase:
         want, unless = self._flag_arg(want, "select / want"), self._flag_arg(unless, "unless")
         if out is None:
             out = self.values
-        if not _on_dev(out, b, (self._torch.float32,), (b.num_envs,)):
+        if not on_device(out, b._dev_index, (self._torch.float32,), (b.num_envs,)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(b.num_envs,)} on {b.device}")
         return obs, codes, want, unless, out
 
@@ -371,8 +361,7 @@ class Policy(_PolicyBase):
                 raise ValueError(f"state dict has towers {towers}, the policy {self.towers}")
         _check_tensor_shapes(self.towers, tensors, self.batch.obs_dim)
         dev = self.batch.device
-        devt = [[tuple(torch.as_tensor(x).detach().to(device=dev, dtype=torch.float32).contiguous() for x in wb)
-                 for wb in tw] for tw in tensors]
+        devt = [[tuple(_to_dev_f32(x, dev) for x in wb) for wb in tw] for tw in tensors]
         keep = []
         arr = _tower_structs(self.towers, devt, keep)
         with torch.cuda.device(dev):
@@ -530,7 +519,7 @@ def _lstm_structs(hidden, n_towers, tensors=None, keep=None):
         if tensors is None:
             continue
         for name, x in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), tensors[i]):
-            setattr(arr[i], name, x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())
+            setattr(arr[i], name, C.ptr(x))
             if keep is not None:
                 keep.append(x)
     return arr
@@ -587,13 +576,11 @@ def lstm_host_forward(hidden, towers, lstm_tensors, mlp_tensors, activation, obs
     actions = np.zeros(n, np.int32)
     logits = np.zeros((n, A), np.float32)
     values = np.zeros(n, np.float32) if nt == 2 else None
-    P = ctypes.c_void_p
     C.check(C.lib().pe_policy_lstm_forward_host(
-        n, D, nt, larr, tarr, ACTIVATIONS[activation], obs.ctypes.data_as(P),
-        start.ctypes.data_as(P) if start is not None else None, hs.ctypes.data_as(P), cs.ctypes.data_as(P),
+        n, D, nt, larr, tarr, ACTIVATIONS[activation], C.ptr(obs), C.ptr(start), C.ptr(hs), C.ptr(cs),
         C.PE_POLICY_ARGMAX if deterministic else C.PE_POLICY_SAMPLE, int(seed) & 0xFFFFFFFFFFFFFFFF,
-        int(env_id_offset) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, actions.ctypes.data_as(P), logits.ctypes.data_as(P),
-        values.ctypes.data_as(P) if values is not None else None), "pe_policy_lstm_forward_host")
+        int(env_id_offset) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, C.ptr(actions), C.ptr(logits), C.ptr(values)),
+        "pe_policy_lstm_forward_host")
     return (actions, logits, values), [(hs[i], cs[i]) for i in range(nt)]
 
 
@@ -640,9 +627,8 @@ class RecurrentPolicy(_PolicyBase):
         _check_lstm_shapes(self.hidden, len(self.towers), lstm, self.batch.obs_dim)
         _check_tensor_shapes(self.towers, mlp, self.hidden)
         dev = self.batch.device
-        up = lambda x: torch.as_tensor(x).detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-        dl = [tuple(up(x) for x in tw) for tw in lstm]
-        dm = [[tuple(up(x) for x in wb) for wb in tw] for tw in mlp]
+        dl = [tuple(_to_dev_f32(x, dev) for x in tw) for tw in lstm]
+        dm = [[tuple(_to_dev_f32(x, dev) for x in wb) for wb in tw] for tw in mlp]
         keep = []
         larr = _lstm_structs(self.hidden, len(self.towers), dl, keep)
         tarr = _tower_structs(self.towers, dm, keep)
@@ -709,7 +695,7 @@ class RecurrentPolicy(_PolicyBase):
             if len(out) != len(self.towers) or any(len(pair) != 2 for pair in out):
                 raise ValueError(f"out must be {len(self.towers)} (h, c) pairs")
             for x in (x for pair in out for x in pair):
-                if not _on_dev(x, b, (torch.float32,), shape):
+                if not on_device(x, b._dev_index, (torch.float32,), shape):
                     raise ValueError(f"out tensors must be contiguous float32 of shape {shape} on {b.device}")
         res = []
         for i in range(len(self.towers)):
@@ -726,12 +712,12 @@ class RecurrentPolicy(_PolicyBase):
     def set_states(self, states):
         """Replace the state: [(h, c), ..] per tower, [n, H] each (device tensors are read in
         place on the current stream; anything else is uploaded first)."""
-        torch, b = self._torch, self.batch
+        b = self.batch
         if len(states) != len(self.towers):
             raise ValueError(f"expected {len(self.towers)} (h, c) pairs")
         dev = []
         for h, c in states:
-            pair = tuple(torch.as_tensor(x).detach().to(device=b.device, dtype=torch.float32).contiguous() for x in (h, c))
+            pair = tuple(_to_dev_f32(x, b.device) for x in (h, c))
             if any(tuple(x.shape) != (b.num_envs, self.hidden) for x in pair):
                 raise ValueError(f"states must be [n, H] = {(b.num_envs, self.hidden)}")
             dev.append(pair)

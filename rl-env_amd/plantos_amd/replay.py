@@ -33,21 +33,15 @@ draws fresh random numbers.  Every output is defined bit for bit by the host twi
 (`host_select`, `host_sample_indices`, `host_target`, `HostRing`), which need no device.
 Multi-GPU: one collector per shard; exploration is keyed by the global env id.
 """
-import ctypes
-
 import numpy as np
 
 from . import _capi as C
-from .codes import CODE_POS, CODE_VIS, code_table, encode_obs
-from .policy import Policy, RecurrentPolicy, _on_dev
+from ._capi import ptr as _p
+from ._collector import Collector, check_autoreset, check_policy_batch, unwrap
+from .codes import encode_obs
+from .policy import Policy, RecurrentPolicy
 
 U64 = 0xFFFFFFFFFFFFFFFF
-
-
-def _p(x):
-    if x is None:
-        return None
-    return ctypes.c_void_p(x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())
 
 
 def linear_eps(progress, initial=1.0, final=0.05, fraction=0.7):
@@ -78,12 +72,10 @@ def check_replay_args(batch, policy, buffer_size):
         raise ValueError("policy must be a plantos_amd.Policy")
     if len(policy.towers) != 1:
         raise ValueError("a Q-network is one tower: the policy must not have a value tower")
-    if policy.batch is not batch:
-        raise ValueError("the policy was made for another batch")
+    check_policy_batch(policy, batch)
     if not batch.obs_codes:
         raise ValueError("the replay ring stores obs byte codes: the batch must be created with obs_codes=True")
-    if not batch.cfg.autoreset:
-        raise ValueError("replay collection needs a batch with autoreset=True")
+    check_autoreset(batch, "replay collection needs")
     n = int(batch.num_envs)
     if int(buffer_size) < n:
         raise ValueError(f"buffer_size {buffer_size} holds less than one row of {n} transitions")
@@ -183,11 +175,6 @@ class HostRing:
 
 
 # ------------------------------------------------------------------ the kernels on tensors
-def _stream(t):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def select_device(greedy, A, eps, ctrl, seed, env_id_offset, actions, explored=None):
     """pe_replay_select on device tensors (contiguous, on greedy's device), current stream:
     greedy i32 [n], eps f32 [1], ctrl i64 [PE_REPLAY_CTRL_WORDS], actions i32 [n] (may be
@@ -195,8 +182,8 @@ def select_device(greedy, A, eps, ctrl, seed, env_id_offset, actions, explored=N
     import torch
     with torch.cuda.device(greedy.device):
         C.check(C.lib().pe_replay_select(greedy.shape[0], int(A), _p(greedy), _p(eps), _p(ctrl), int(seed) & U64,
-                                         int(env_id_offset) & 0xFFFFFFFF, _p(actions), _p(explored), _stream(greedy)),
-                "pe_replay_select")
+                                         int(env_id_offset) & 0xFFFFFFFF, _p(actions), _p(explored),
+                                         C.stream_ptr(greedy.device)), "pe_replay_select")
 
 
 def store_device(ring, geometry, obs, actions, next_obs, reward, terminated, truncated, terminal_obs, ctrl,
@@ -214,7 +201,7 @@ def store_device(ring, geometry, obs, actions, next_obs, reward, terminated, tru
         C.check(C.lib().pe_replay_store(n, K, G, R, Cn, _p(obs), _p(actions), _p(next_obs), _p(reward), _p(terminated),
                                         _p(truncated), _p(terminal_obs), _p(episode_return), _p(episode_length),
                                         _p(ring[0]), _p(ring[1]), _p(ring[2]), _p(ring[3]), _p(ring[4]), _p(ep_count),
-                                        _p(ep_return_sum), _p(ep_length_sum), _p(ctrl), _stream(obs)),
+                                        _p(ep_return_sum), _p(ep_length_sum), _p(ctrl), C.stream_ptr(obs.device)),
                 "pe_replay_store")
 
 
@@ -228,7 +215,7 @@ def sample_device(ring, ctrl, seed, obs, next_obs, actions, rewards, dones, indi
     with torch.cuda.device(obs.device):
         C.check(C.lib().pe_replay_sample(B, n, K, D, _p(ring[0]), _p(ring[1]), _p(ring[2]), _p(ring[3]), _p(ring[4]),
                                          int(seed) & U64, _p(ctrl), _p(obs), _p(next_obs), _p(actions), _p(rewards),
-                                         _p(dones), _p(indices), _stream(obs)), "pe_replay_sample")
+                                         _p(dones), _p(indices), C.stream_ptr(obs.device)), "pe_replay_sample")
 
 
 def target_device(q_next, rewards, dones, gamma, out):
@@ -238,7 +225,7 @@ def target_device(q_next, rewards, dones, gamma, out):
     B, A = q_next.shape
     with torch.cuda.device(q_next.device):
         C.check(C.lib().pe_replay_target(B, A, _p(q_next), _p(rewards), _p(dones), float(gamma), _p(out),
-                                         _stream(q_next)), "pe_replay_target")
+                                         C.stream_ptr(q_next.device)), "pe_replay_target")
 
 
 class ReplayBatch:
@@ -266,7 +253,7 @@ class ReplayBatch:
         B, D = codes.shape
         if out is None:
             out = torch.empty((B, D), dtype=torch.float32, device=b.device)
-        elif not _on_dev(out, b, (torch.float32,), (B, D)):
+        elif not C.on_device(out, b._dev_index, (torch.float32,), (B, D)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(B, D)} on {b.device}")
         with torch.cuda.device(b.device):
             C.check(C.lib().pe_expand_obs_codes(b.handle, 1, B, _p(codes), 0, _p(out), None, None, None, b._stream()),
@@ -282,7 +269,7 @@ class ReplayBatch:
         return self._f32(self.next_obs, out)
 
 
-class ReplayCollector:
+class ReplayCollector(Collector):
     """Collects DQN transitions of every env of an ``obs_codes`` PlantOSBatch (or a
     PlantOSVecEnv's batch) under a one-tower Q-network Policy, entirely on the device.
 
@@ -294,13 +281,10 @@ class ReplayCollector:
     autoreset, and buffer_size < n."""
 
     def __init__(self, batch_or_venv, q_policy, buffer_size=2_000_000, seed=0):
-        import torch
-        self._torch = torch
-        b = self.batch = getattr(batch_or_venv, "batch", batch_or_venv)
+        b = unwrap(batch_or_venv)
         self.K = K = check_replay_args(b, q_policy, buffer_size)
-        b.handle  # a closed batch raises here
-        q_policy._handle()
-        self.policy = q_policy
+        self._attach(b, q_policy)
+        torch = self._torch
         self.seed = int(seed) & U64
         self.env_id_offset = int(b.cfg.env_id_offset)
         self.geometry = (int(b.cfg.grid_size), int(b.cfg.lidar_range), int(b.cfg.lidar_channels))
@@ -317,13 +301,8 @@ class ReplayCollector:
         self.eps = 1.0
         self.actions = torch.zeros(n, dtype=i32, device=dev)      # the actions last taken
         self.greedy = torch.zeros(n, dtype=i32, device=dev)       # the Q-network's argmax behind them
-        self.ep_count = torch.zeros(n, dtype=i32, device=dev)
-        self.ep_return_sum = torch.zeros(n, dtype=torch.float64, device=dev)
-        self.ep_length_sum = torch.zeros(n, dtype=i32, device=dev)
         self._ios = [b.new_io(), b.new_io()]
         self._views = [b.io_views(io) for io in self._ios]
-        self._no_mask = torch.zeros(n, dtype=u8, device=dev)
-        self._primed = False
         self._batches = {}
 
     # ----------------------------------------------------------------- counters, schedule
@@ -348,22 +327,6 @@ class ReplayCollector:
         """u8 [n, D]: the obs codes the next collect() step acts on (after the first collect)."""
         return self._views[0][0]
 
-    # ----------------------------------------------------------------- row 0
-    def _prime(self):
-        """The first obs: the batch's current obs (pe_reset with an empty mask writes every
-        env's current obs and resets none), encoded to codes."""
-        torch, b = self._torch, self.batch
-        x = b.reset(mask=self._no_mask).to(torch.float64)
-        G, R, Cn = self.geometry
-        codes = self._views[0][0]
-        lid = x[:, :5 * Cn].view(-1, Cn, 5)
-        out = torch.where(lid != 0, R + 1, 0)
-        out[..., 0] = torch.round(lid[..., 0] * R).to(out.dtype)
-        codes[:, :5 * Cn] = out.view(-1, 5 * Cn).to(torch.uint8)
-        codes[:, 5 * Cn:5 * Cn + 2] = (torch.round(x[:, 5 * Cn:5 * Cn + 2] * G) + CODE_POS).to(torch.uint8)
-        codes[:, 5 * Cn + 2:] = (torch.round(x[:, 5 * Cn + 2:] * 10) + CODE_VIS).to(torch.uint8)
-        self._primed = True
-
     # ----------------------------------------------------------------- hot path
     def collect(self, k=1):
         """k times: Q-network argmax on the current obs -> epsilon-greedy select -> step ->
@@ -377,7 +340,7 @@ class ReplayCollector:
         if k < 1:
             raise ValueError(f"k must be >= 1, got {k}")
         if not self._primed:
-            self._prime()
+            self._prime_obs(self._views[0][0])  # the first obs: the batch's current one, as codes
         b, pol = self.batch, self.policy
         A = pol.towers[0][-1]
         cur = 0
@@ -423,7 +386,7 @@ class ReplayCollector:
         B = mb.obs.shape[0]
         if out is None:
             out = mb.targets
-        elif not _on_dev(out, b, (torch.float32,), (B,)):
+        elif not C.on_device(out, b._dev_index, (torch.float32,), (B,)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(B,)} on {b.device}")
         target_policy.act_rows(mb.next_obs, out=(mb._next_actions, mb._next_q, None))
         target_device(mb._next_q, mb.rewards, mb.dones, gamma, out)

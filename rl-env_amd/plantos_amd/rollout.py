@@ -25,20 +25,14 @@ Every output is defined bit for bit by the host twins (`host_record`, `host_gae`
 `RolloutCollector.host_rollout`, `RecurrentRolloutCollector.host_rollout`), which need no
 device.
 """
-import ctypes
-
 import numpy as np
 
 from . import _capi as C
-from .policy import Policy, RecurrentPolicy, _on_dev, lstm_host_forward
+from ._capi import ptr as _p
+from ._collector import Collector, check_autoreset, check_policy_batch, unwrap
+from .policy import Policy, RecurrentPolicy, lstm_host_forward
 
 ROW_ALIGN = 512  # bytes: every row of the buffer starts as aligned as a fresh torch allocation
-
-
-def _p(x):
-    if x is None:
-        return None
-    return ctypes.c_void_p(x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())
 
 
 def host_record(logits, actions, reward, terminated, truncated, gamma, terminal_value=None, episode_return=None,
@@ -101,8 +95,7 @@ def record_device(logits, actions, reward, terminated, truncated, gamma, log_pro
         C.check(C.lib().pe_rollout_record(
             n, A, _p(logits), _p(actions), _p(reward), _p(terminated), _p(truncated), _p(terminal_value),
             _p(episode_return), _p(episode_length), float(gamma), _p(log_prob), _p(reward_out), _p(start_next),
-            _p(ep_count), _p(ep_return_sum), _p(ep_length_sum),
-            ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)), "pe_rollout_record")
+            _p(ep_count), _p(ep_return_sum), _p(ep_length_sum), C.stream_ptr(logits.device)), "pe_rollout_record")
 
 
 def gae_device(rewards, values, starts, last_values, gamma, gae_lambda, advantages, returns):
@@ -121,9 +114,7 @@ def gae_device(rewards, values, starts, last_values, gamma, gae_lambda, advantag
     with torch.cuda.device(rewards.device):
         C.check(C.lib().pe_rollout_gae(T, n, rs(rewards), rs(values), starts.stride(0), rs(advantages), _p(rewards),
                                        _p(values), _p(starts), _p(last_values), float(gamma), float(gae_lambda),
-                                       _p(advantages), _p(returns),
-                                       ctypes.c_void_p(torch.cuda.current_stream(rewards.device).cuda_stream)),
-                "pe_rollout_gae")
+                                       _p(advantages), _p(returns), C.stream_ptr(rewards.device)), "pe_rollout_gae")
 
 
 class Rollout:
@@ -155,25 +146,19 @@ class Rollout:
         return self._c._obs_f32(out)
 
 
-class _Collector:
+class _Collector(Collector):
     """What the two collectors share: the argument checks after the policy's kind, the storage
     rows, row 0 and the obs view."""
 
-    def _setup(self, batch, policy, n_steps, gamma, gae_lambda, bootstrap_timeouts, deterministic):
-        import torch
-        self._torch = torch
-        b = self.batch = batch
+    def _setup(self, b, policy, n_steps, gamma, gae_lambda, bootstrap_timeouts, deterministic):
         if len(policy.towers) != 2:
             raise ValueError("a rollout needs values: the policy must have a value tower")
-        if policy.batch is not b:
-            raise ValueError("the policy was made for another batch")
+        check_policy_batch(policy, b)
         if int(n_steps) < 1:
             raise ValueError(f"n_steps must be >= 1, got {n_steps}")
-        b.handle  # a closed batch raises here
-        policy._handle()
-        if not b.cfg.autoreset:
-            raise ValueError("a rollout needs a batch with autoreset=True")
-        self.policy = policy
+        self._attach(b, policy)
+        check_autoreset(b, "a rollout needs")
+        torch = self._torch
         self.n_steps = T = int(n_steps)
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
         self.bootstrap_timeouts, self.deterministic = bool(bootstrap_timeouts), bool(deterministic)
@@ -203,11 +188,6 @@ class _Collector:
         self.last_values = torch.zeros(n, dtype=f32, device=dev)
         self.terminal_values = torch.zeros(n, dtype=f32, device=dev)
         self._logits = torch.zeros((n, A), dtype=f32, device=dev)
-        self._no_mask = torch.zeros(n, dtype=torch.uint8, device=dev)
-        self.ep_count = torch.zeros(n, dtype=i32, device=dev)
-        self.ep_return_sum = torch.zeros(n, dtype=torch.float64, device=dev)
-        self.ep_length_sum = torch.zeros(n, dtype=i32, device=dev)
-        self._primed = False
         self._rollout = Rollout(
             self, obs=self._obs, actions=self.actions, rewards=self._rewards, episode_starts=self._starts_all[:T],
             values=self.values, log_probs=self.log_probs, advantages=self.advantages, returns=self.returns,
@@ -225,29 +205,15 @@ class _Collector:
 
     # ----------------------------------------------------------------- row 0
     def _prime(self):
-        """Row 0 of the first collect: the batch's current obs (pe_reset with an empty mask
-        writes every env's current obs and resets none), as codes on an ``obs_codes`` batch;
-        every env starts an episode."""
-        torch, b = self._torch, self.batch
-        if not b.obs_codes:
-            b.reset(mask=self._no_mask, obs=self._row_views[0][0])
-        else:
-            x = b.reset(mask=self._no_mask).to(torch.float64)
-            Cn, R, G = int(b.cfg.lidar_channels), int(b.cfg.lidar_range), int(b.cfg.grid_size)
-            codes = self._row_views[0][0]
-            lid = x[:, :5 * Cn].view(-1, Cn, 5)
-            out = torch.where(lid != 0, R + 1, 0)
-            out[..., 0] = torch.round(lid[..., 0] * R).to(out.dtype)
-            codes[:, :5 * Cn] = out.view(-1, 5 * Cn).to(torch.uint8)
-            codes[:, 5 * Cn:5 * Cn + 2] = (torch.round(x[:, 5 * Cn:5 * Cn + 2] * G) + 96).to(torch.uint8)
-            codes[:, 5 * Cn + 2:] = (torch.round(x[:, 5 * Cn + 2:] * 10) + 80).to(torch.uint8)
+        """Row 0 of the first collect: the batch's current obs (as codes on an ``obs_codes``
+        batch); every env starts an episode."""
+        self._prime_obs(self._row_views[0][0])
         self._start[0].fill_(1)
-        self._primed = True
 
     def _obs_f32(self, out=None):
         torch, b = self._torch, self.batch
         T, n, D = self.n_steps, b.num_envs, b.obs_dim
-        if out is not None and not _on_dev(out, b, (torch.float32,), (T * n, D)):
+        if out is not None and not C.on_device(out, b._dev_index, (torch.float32,), (T * n, D)):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(T * n, D)} on {b.device}")
         if not b.obs_codes:
             if out is None:
@@ -285,8 +251,7 @@ class RolloutCollector(_Collector):
             raise ValueError("a RecurrentPolicy's rollouts are collected by RecurrentRolloutCollector")
         if not isinstance(policy, Policy):
             raise ValueError("policy must be a plantos_amd.Policy")
-        self._setup(getattr(batch_or_venv, "batch", batch_or_venv), policy, n_steps, gamma, gae_lambda,
-                    bootstrap_timeouts, deterministic)
+        self._setup(unwrap(batch_or_venv), policy, n_steps, gamma, gae_lambda, bootstrap_timeouts, deterministic)
 
     # ----------------------------------------------------------------- hot path
     def collect(self):
@@ -376,8 +341,7 @@ class RecurrentRolloutCollector(_Collector):
             raise ValueError("policy must be a plantos_amd.RecurrentPolicy (RolloutCollector collects a Policy's rollouts)")
         if state_snapshots not in ("first", "all"):
             raise ValueError(f"state_snapshots must be 'first' or 'all', got {state_snapshots!r}")
-        self._setup(getattr(batch_or_venv, "batch", batch_or_venv), policy, n_steps, gamma, gae_lambda,
-                    bootstrap_timeouts, deterministic)
+        self._setup(unwrap(batch_or_venv), policy, n_steps, gamma, gae_lambda, bootstrap_timeouts, deterministic)
         torch, b = self._torch, self.batch
         self.state_snapshots = state_snapshots
         S = self.n_steps if state_snapshots == "all" else 1

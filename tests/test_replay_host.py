@@ -179,6 +179,32 @@ def test_host_ring_rules():
     assert ring.ep_count.sum() > 0 and ring.ep_length_sum.sum() > 0
 
 
+@pytest.mark.parametrize("G, Cn, R", [(20, 16, 6), (21, 10, 2), (32, 24, 9), (64, 64, 32)])
+def test_encode_obs_returns_the_codes(G, Cn, R):
+    """codes.encode_obs, the one Python statement of pe_replay_math.hpp's replay_encode: code rows
+    that hold every distance code 0..R, both one-hot codes, every position code and the visit
+    codes 80..90, expanded with code_table, come back exactly -- from the numpy form and from the
+    torch form on CPU tensors.  Codes 91..95 expand to the same float as 90 (a visit count past 10
+    reads as 1.0), so the encoder cannot give them back and they are left out."""
+    import torch
+    from plantos_amd.codes import CODE_POS, CODE_VIS, code_table, encode_obs
+    rows, D = max(G, R + 1, 11), 5 * Cn + 27
+    i, c = np.arange(rows)[:, None], np.arange(D)[None, :]
+    codes = np.where(c % 5 == 0, (i + c // 5) % (R + 1), ((i + c) % 2) * (R + 1))      # lidar: distance, one-hot
+    codes = np.where(c >= 5 * Cn, CODE_POS + (i + c) % G, codes)                       # the two position columns
+    codes = np.where(c >= 5 * Cn + 2, CODE_VIS + (i + c) % 11, codes).astype(np.uint8)  # the 25 visit columns
+    assert set(codes[:, 0:5 * Cn:5].ravel()) == set(range(R + 1))
+    assert set(codes[:, 1:5 * Cn:5].ravel()) == {0, R + 1}
+    assert set(codes[:, 5 * Cn:5 * Cn + 2].ravel()) == set(range(CODE_POS, CODE_POS + G))
+    assert set(codes[:, 5 * Cn + 2:].ravel()) == set(range(CODE_VIS, CODE_VIS + 11))
+    obs = code_table(G, R)[codes]
+    assert obs.dtype == np.float32 and obs.shape == (rows, D)
+    got = encode_obs(obs, G, Cn, R)
+    assert isinstance(got, np.ndarray) and got.dtype == np.uint8 and np.array_equal(got, codes)
+    got = encode_obs(torch.from_numpy(obs), G, Cn, R)
+    assert type(got) is torch.Tensor and got.dtype is torch.uint8 and np.array_equal(got.numpy(), codes)
+
+
 def _stub_policy(cls, towers, batch):
     p = object.__new__(cls)
     p.towers, p.batch = towers, batch
