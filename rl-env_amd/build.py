@@ -34,7 +34,7 @@ SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST, SRC
 DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in
                   ("pe_device.hpp", "pe_fast.hpp", "pe_quad.hpp", "pe_coop.hpp", "pe_handle.hpp", "pe_far.hpp",
                    "pe_plan.hpp", "pe_host.hpp", "pe_policy_math.hpp", "pe_policy_impl.hpp", "pe_policy_plan.hpp",
-                   "pe_rollout_math.hpp", "pe_replay_math.hpp")] + [
+                   "pe_rollout_math.hpp", "pe_rollout_minibatch.h", "pe_replay_math.hpp")] + [
     os.path.join(REPO, "include", "plantos_batch.h"), os.path.join(HERE, "tools_gen_lidar.py")]
 OUT = os.path.join(HERE, "plantos_amd", "libplantos_hip.so")
 OBJ_DIR = os.path.join(REPO, "build", "obj")

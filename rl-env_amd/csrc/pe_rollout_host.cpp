@@ -1,11 +1,14 @@
 // pe_rollout_host.cpp -- the host twins of pe_rollout_record and pe_rollout_gae
-// (include/plantos_batch.h, "Rollout collection"): the definitions executed literally on
-// host arrays with the functions of pe_rollout_math.hpp, which the kernels (pe_rollout.hip)
-// include too; and the argument rules both sides share.  Plain C++: no handle, no device.
+// (include/plantos_batch.h, "Rollout collection") and of the rollout minibatches
+// (pe_rollout_minibatch.h): the definitions executed literally on host arrays with the
+// functions of pe_rollout_math.hpp, which the kernels (pe_rollout.hip) include too; and the
+// argument rules both sides share.  Plain C++: no handle, no device.
+#include <algorithm>
 #include <string>
 
 #include "../../include/plantos_batch.h"
 #include "pe_rollout_math.hpp"
+#include "pe_rollout_minibatch.h"
 
 extern "C" int pe_internal_set_error(int code, const char* msg);
 
@@ -88,6 +91,104 @@ int pe_rollout_gae_host(int32_t T, int32_t n, int64_t reward_stride, int64_t val
       returns[(int64_t)t * out_stride + e] = gae_return(last, v);
     }
   }
+  return PE_OK;
+}
+
+// ---------------------------------------------------------------- rollout minibatches
+int pe_internal_rollout_minibatch_check(const pe_rollout_mb* a) {
+  auto fail = [](const std::string& m) { return pe_internal_set_error(PE_ERR_ARG, ("rollout minibatch: " + m).c_str()); };
+  if (!a) return fail("null argument block");
+  if (a->mode != PE_MB_ROWS && a->mode != PE_MB_ENVS) return fail("mode must be PE_MB_ROWS or PE_MB_ENVS");
+  if (a->T < 1 || a->n < 1 || a->D < 1) return fail("T, n and D must be >= 1");
+  if (a->B < 1) return fail("the batch size must be >= 1, got " + std::to_string(a->B));
+  const int64_t rows = (int64_t)a->T * a->n;
+  if (rows > 2147483647LL) return fail("T * n must be <= 2^31 - 1, got " + std::to_string(rows));
+  const int64_t M = a->mode == PE_MB_ROWS ? rows : (int64_t)a->n;
+  const int64_t R = a->mode == PE_MB_ROWS ? (int64_t)a->B : (int64_t)a->T * a->B;
+  if (R > 2147483647LL) return fail("T * B must be <= 2^31 - 1");
+  const int64_t nmb = (M + a->B - 1) / a->B;
+  if (!a->ctrl && a->k >= (uint64_t)nmb)
+    return fail("k must be < ceil(M / B) = " + std::to_string(nmb) + ", got " + std::to_string(a->k));
+  const int64_t row_bytes = (int64_t)a->n * a->D * (a->obs_f32 ? 4 : 1);
+  if (!a->buf || ((uintptr_t)a->buf & 3) != 0) return fail("null or misaligned obs storage");
+  if (a->obs_f32 && (a->stride & 3) != 0) return fail("the row stride of f32 storage must be a multiple of 4");
+  if (((uintptr_t)a->out_obs & 15) != 0 || ((uintptr_t)a->out_codes & 3) != 0)
+    return fail("out_obs must be 16-byte aligned and out_codes 4-byte aligned");
+  if (a->T > 1 && a->stride < row_bytes) return fail("the obs row stride is shorter than a row");
+  if (a->buf_bytes < (int64_t)(a->T - 1) * a->stride + row_bytes) return fail("buf_bytes does not cover T obs rows");
+  if (!a->obs_f32 && !a->table) return fail("code storage needs the code table");
+  if (a->obs_f32 && a->out_codes) return fail("f32 storage has no codes to return");
+  if (!a->actions || !a->values || !a->log_probs || !a->advantages || !a->returns)
+    return fail("null actions / values / log_probs / advantages / returns");
+  if (a->s_actions < a->n || a->s_values < a->n || a->s_log_probs < a->n || a->s_advantages < a->n || a->s_returns < a->n)
+    return fail("every row stride must be >= n");
+  if (!a->indices || !a->out_obs || !a->out_actions || !a->out_values || !a->out_log_probs || !a->out_advantages ||
+      !a->out_returns)
+    return fail("null output");
+  if (a->mode == PE_MB_ENVS && (!a->starts || !a->out_starts || a->s_starts < a->n))
+    return fail("env mode needs starts (row stride >= n) and out_starts");
+  if (a->n_states < 0 || a->n_states > PE_MB_MAX_STATES) return fail("n_states must be in 0..4");
+  if (a->n_states > 0) {
+    if (a->mode != PE_MB_ENVS) return fail("states are gathered in env mode only");
+    if (a->H < 1) return fail("H must be >= 1 with states");
+    for (int s = 0; s < a->n_states; ++s)
+      if (!a->state_src[s] || !a->state_dst[s]) return fail("states requested but a state array is null");
+  }
+  return PE_OK;
+}
+
+int pe_internal_rollout_perm_host(int64_t M, uint64_t seed, uint64_t epoch, int32_t mode, int64_t first, int64_t count,
+                                  int32_t* out) {
+  auto fail = [](const std::string& m) { return pe_internal_set_error(PE_ERR_ARG, ("rollout perm: " + m).c_str()); };
+  if (M < 1 || M > 2147483647LL) return fail("M must be in 1..2^31 - 1, got " + std::to_string(M));
+  if (mode != PE_MB_ROWS && mode != PE_MB_ENVS) return fail("mode must be PE_MB_ROWS or PE_MB_ENVS");
+  if (first < 0 || count < 0 || first > M - count) return fail("positions first .. first + count must lie in [0, M]");
+  if (count > 0 && !out) return fail("null out");
+  const uint32_t domain = mode == PE_MB_ROWS ? kDomainPermRows : kDomainPermEnvs;
+  for (int64_t j = 0; j < count; ++j) out[j] = (int32_t)rollout_perm(seed, epoch, domain, (uint32_t)M, (uint32_t)(first + j));
+  return PE_OK;
+}
+
+namespace {
+// One pass of the normalisation's summation order (pe_rollout_math.hpp): of (double)a, or of
+// norm_square(a, mean).
+double norm_pass(int64_t N, int64_t count, int64_t ld, const float* a, bool square, double mean) {
+  double total = 0.0;
+  for (int64_t base = 0; base < N; base += kNormChunk) {
+    const int64_t len = std::min<int64_t>(kNormChunk, N - base);
+    double s[kNormLanes];
+    for (int l = 0; l < kNormLanes; ++l) s[l] = 0.0;
+    for (int64_t q = 0; q < len; ++q) {
+      const int64_t i = base + q;
+      const float v = a[(i / count) * ld + i % count];
+      s[q % kNormLanes] += square ? norm_square(v, mean) : (double)v;
+    }
+    for (int h = kNormLanes / 2; h >= 1; h /= 2)
+      for (int l = 0; l < h; ++l) s[l] += s[l + h];
+    total += s[0];
+  }
+  return total;
+}
+}  // namespace
+
+int pe_internal_rollout_adv_norm_host(int32_t rows, int32_t count, int64_t ld, const float* a, float* out) {
+  auto fail = [](const std::string& m) { return pe_internal_set_error(PE_ERR_ARG, ("rollout adv norm: " + m).c_str()); };
+  if (rows < 1 || count < 0 || ld < count) return fail("rows must be >= 1, count >= 0 and ld >= count");
+  if (!a || !out) return fail("null a / out");
+  const int64_t N = (int64_t)rows * count;
+  if (N > 2147483647LL) return fail("rows * count must be <= 2^31 - 1");
+  float mean = 0.0f, sd = 0.0f;
+  if (N >= 2) {
+    const double m = norm_pass(N, count, ld, a, false, 0.0) / (double)N;
+    const double var = norm_pass(N, count, ld, a, true, m) / (double)(N - 1);
+    mean = (float)m;
+    sd = norm_sqrt_f32(var);
+  }
+  for (int64_t t = 0; t < rows; ++t)
+    for (int64_t j = 0; j < count; ++j) {
+      const float v = a[t * ld + j];
+      out[t * ld + j] = N >= 2 ? norm_apply(v, mean, sd) : v;
+    }
   return PE_OK;
 }
 

@@ -10,14 +10,18 @@ Public surface:
                     bootstrap and GAE (SB3's collect_rollouts); returns a Rollout
   RecurrentRolloutCollector  the same under a RecurrentPolicy (sb3_contrib's RecurrentPPO), with
                     snapshots of the LSTM state in the Rollout
+  RolloutMinibatch  a shuffled minibatch of a Rollout, gathered on the device (SB3's
+                    RolloutBuffer.get): Rollout.minibatches / env_minibatches / next_minibatch
   ReplayCollector   DQN's collection on the device: epsilon-greedy exploration, the transition
                     ring, uniform minibatch sampling (a ReplayBatch) and TD targets
 """
 from .batch import PlantOSBatch  # noqa: F401
 from .policy import Policy, RecurrentPolicy  # noqa: F401
 from .replay import ReplayBatch, ReplayCollector, linear_eps  # noqa: F401
-from .rollout import RecurrentRolloutCollector, Rollout, RolloutCollector  # noqa: F401
+from .rollout import (RecurrentRolloutCollector, Rollout, RolloutCollector, RolloutMinibatch,  # noqa: F401
+                      host_adv_norm, host_minibatch_indices)
 from .vec_env import PlantOSVecEnv, PlantOSVectorEnv  # noqa: F401
 
 __all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy", "Rollout",
-           "RolloutCollector", "RecurrentRolloutCollector", "ReplayBatch", "ReplayCollector", "linear_eps"]
+           "RolloutCollector", "RecurrentRolloutCollector", "ReplayBatch", "ReplayCollector", "linear_eps",
+           "RolloutMinibatch", "host_minibatch_indices", "host_adv_norm"]

@@ -84,6 +84,29 @@ class PEPolicyPlanInfo(ctypes.Structure):
                 ("state_floats", ctypes.c_uint64)]
 
 
+PE_MB_ROWS, PE_MB_ENVS = 0, 1
+PE_MB_MAX_STATES = 4
+
+
+class PERolloutMb(ctypes.Structure):
+    """pe_rollout_mb (csrc/pe_rollout_minibatch.h): one rollout minibatch gather."""
+    _fields_ = [
+        ("mode", ctypes.c_int32), ("T", ctypes.c_int32), ("n", ctypes.c_int32), ("D", ctypes.c_int32),
+        ("B", ctypes.c_int32), ("obs_f32", ctypes.c_int32), ("n_states", ctypes.c_int32), ("H", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("epoch", ctypes.c_uint64), ("k", ctypes.c_uint64),
+        ("buf", ctypes.c_void_p), ("stride", ctypes.c_int64), ("buf_bytes", ctypes.c_int64),
+        ("table", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("values", ctypes.c_void_p),
+        ("log_probs", ctypes.c_void_p), ("advantages", ctypes.c_void_p), ("returns", ctypes.c_void_p),
+        ("starts", ctypes.c_void_p), ("s_actions", ctypes.c_int64), ("s_values", ctypes.c_int64),
+        ("s_log_probs", ctypes.c_int64), ("s_advantages", ctypes.c_int64), ("s_returns", ctypes.c_int64),
+        ("s_starts", ctypes.c_int64), ("state_src", ctypes.c_void_p * 4), ("ctrl", ctypes.c_void_p),
+        ("count", ctypes.c_void_p), ("indices", ctypes.c_void_p), ("out_obs", ctypes.c_void_p),
+        ("out_codes", ctypes.c_void_p), ("out_actions", ctypes.c_void_p), ("out_values", ctypes.c_void_p),
+        ("out_log_probs", ctypes.c_void_p), ("out_advantages", ctypes.c_void_p), ("out_returns", ctypes.c_void_p),
+        ("out_starts", ctypes.c_void_p), ("state_dst", ctypes.c_void_p * 4),
+    ]
+
+
 class PlantOSNativeError(RuntimeError):
     pass
 
@@ -173,13 +196,20 @@ def _signatures():
         "pe_internal_plan": (INT, [CP, I32, I32, ctypes.POINTER(PEPlanInfo)]),
         "pe_internal_policy_plan": (INT, plan + [ctypes.POINTER(PEPolicyPlanInfo)]),
         "pe_internal_policy_plan_prec": (INT, plan + [I32, ctypes.POINTER(PEPolicyPlanInfo)]),
+        # csrc/pe_rollout_minibatch.h
+        "pe_internal_rollout_minibatch_check": (INT, [ctypes.POINTER(PERolloutMb)]),
+        "pe_internal_rollout_minibatch": (INT, [ctypes.POINTER(PERolloutMb), P]),
+        "pe_internal_rollout_perm_host": (INT, [I64, U64, U64, I32, I64, I64, P]),
+        "pe_internal_rollout_adv_norm": (INT, [I32, I32, I64, P, P, P, P, P]),
+        "pe_internal_rollout_adv_norm_host": (INT, [I32, I32, I64, P, P]),
     }
     return abi, internal
 
 
 # name -> (restype, [argtypes]).  SIGNATURES: every function of include/plantos_batch.h
 # (tests/test_capi_symbols.py checks each entry against the header's prototype);
-# INTERNAL_SIGNATURES: the plan entry points of csrc/pe_handle.hpp, which are not part of the ABI.
+# INTERNAL_SIGNATURES: the plan entry points of csrc/pe_handle.hpp and the rollout minibatches of
+# csrc/pe_rollout_minibatch.h, which are not part of the ABI.
 SIGNATURES, INTERNAL_SIGNATURES = _signatures()
 EXPORTS = list(SIGNATURES)
 

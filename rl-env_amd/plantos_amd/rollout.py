@@ -21,9 +21,14 @@ RecurrentPPO.collect_rollouts): the LSTM state advances with the steps, the boot
 last_values come from the value-only forward, which leaves it alone, and the Rollout carries
 snapshots of the state for the learner.
 
+A Rollout also hands out shuffled minibatches on the device (SB3's RolloutBuffer.get and the
+advantage normalisation of PPO.train; csrc/pe_rollout_minibatch.h): `ro.minibatches(batch_size,
+epoch, seed)` for row minibatches, `ro.env_minibatches(envs_per_batch, ..)` for whole sequences
+with their starting LSTM state, `ro.next_minibatch(batch_size)` with counters on the device.
+
 Every output is defined bit for bit by the host twins (`host_record`, `host_gae`,
-`RolloutCollector.host_rollout`, `RecurrentRolloutCollector.host_rollout`), which need no
-device.
+`RolloutCollector.host_rollout`, `RecurrentRolloutCollector.host_rollout`,
+`host_minibatch_indices`, `host_adv_norm`), which need no device.
 """
 import numpy as np
 
@@ -117,6 +122,174 @@ def gae_device(rewards, values, starts, last_values, gamma, gae_lambda, advantag
                                        _p(advantages), _p(returns), C.stream_ptr(rewards.device)), "pe_rollout_gae")
 
 
+# ------------------------------------------------------------------ rollout minibatches
+U64 = (1 << 64) - 1
+NORM_CHUNK = 4096  # pe_rollout_math.hpp kNormChunk: elements per chunk of the normalisation's sums
+_MODES = {"rows": C.PE_MB_ROWS, "envs": C.PE_MB_ENVS}
+_MB_IN = ("actions", "values", "log_probs", "advantages", "returns", "starts")
+_MB_OUT = ("indices", "obs", "codes", "actions", "values", "log_probs", "advantages", "returns", "starts")
+
+
+def _uint(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+        raise ValueError(f"{name} must be a non-negative int, got {v!r}")
+    return int(v)
+
+
+def check_minibatch_size(B, name="batch_size"):
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or int(B) < 1:
+        raise ValueError(f"{name} must be an int >= 1, got {B!r}")
+    return int(B)
+
+
+def host_minibatch_indices(M, B, epoch, k, seed=0, domain="rows"):
+    """The source indices i32 [count] of minibatch k of epoch `epoch` (pe_rollout_math.hpp
+    rollout_perm, no device): positions k B .. k B + count - 1, count = min(B, M - k B), of the
+    keyed permutation of [0, M).  domain "rows": M = T * n rows, index = t * n + env; "envs":
+    M = n envs.  ValueError for B < 1, k >= ceil(M / B), M outside 1 .. 2^31 - 1, or an epoch /
+    seed that is no non-negative int."""
+    if domain not in _MODES:
+        raise ValueError(f"domain must be 'rows' or 'envs', got {domain!r}")
+    M, B, k = _uint("M", M), check_minibatch_size(B, "B"), _uint("k", k)
+    epoch, seed = _uint("epoch", epoch), _uint("seed", seed)
+    if M < 1 or k >= -(-M // B):
+        raise ValueError(f"k must be < ceil(M / B) = {-(-M // B)} and M >= 1, got M={M} k={k}")
+    count = min(B, M - k * B)
+    out = np.zeros(count, np.int32)
+    C.check(C.lib().pe_internal_rollout_perm_host(M, seed & U64, epoch & U64, _MODES[domain], k * B, count, _p(out)),
+            "pe_internal_rollout_perm_host")
+    return out
+
+
+def host_adv_norm(a):
+    """The advantage normalisation on a numpy array (pe_internal_rollout_adv_norm_host): f32 [N],
+    or [T, count] numbered row by row; (a - mean) / (std + 1e-8), unbiased std, sums in f64 in
+    the order pe_rollout_math.hpp fixes.  Fewer than 2 elements come back unchanged."""
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim not in (1, 2):
+        raise ValueError("a must be [N] or [T, count]")
+    rows, count = (1, a.shape[0]) if a.ndim == 1 else a.shape
+    out = np.zeros_like(a)
+    if a.size:
+        C.check(C.lib().pe_internal_rollout_adv_norm_host(max(rows, 1), count, count, _p(a), _p(out)),
+                "pe_internal_rollout_adv_norm_host")
+    return out
+
+
+def norm_scratch_len(elements):
+    """f64 words of scratch pe_internal_rollout_adv_norm needs for `elements` elements."""
+    return 2 * (-(-int(elements) // NORM_CHUNK)) if elements > NORM_CHUNK else 0
+
+
+def adv_norm_device(a, out=None, count=None, scratch=None):
+    """pe_internal_rollout_adv_norm on device tensors, current stream: a f32 [cap] or [T, cap]
+    (unit stride over the last axis), out the same layout (None: in place).  count: None (all
+    cap columns) or a device i32 [1] holding how many columns are valid.  scratch: a device f64
+    tensor of norm_scratch_len(a.numel()) words (None: allocated here when needed)."""
+    import torch
+    out = a if out is None else out
+    rows, cap = (1, a.shape[0]) if a.dim() == 1 else a.shape
+    ld = cap if a.dim() == 1 or rows == 1 else a.stride(0)
+    if a.dim() == 2 and rows > 1 and out.stride(0) != ld:
+        raise ValueError("a and out must share their row stride")
+    need = norm_scratch_len(rows * cap)
+    if need and scratch is None:
+        scratch = torch.zeros(need, dtype=torch.float64, device=a.device)
+    if need and scratch.numel() < need:
+        raise ValueError(f"scratch must hold {need} float64 words")
+    with torch.cuda.device(a.device):
+        C.check(C.lib().pe_internal_rollout_adv_norm(rows, cap, ld, _p(count), _p(a), _p(out), _p(scratch),
+                                                     C.stream_ptr(a.device)), "pe_internal_rollout_adv_norm")
+    return out
+
+
+def mb_args(mode, T, n, D, B, buf, stride, fields, outs, obs_f32=False, table=None, seed=0, epoch=0, k=0, ctrl=None,
+            count=None, states=()):
+    """A filled pe_rollout_mb (csrc/pe_rollout_minibatch.h) over device tensors.  mode "rows" /
+    "envs"; buf: the u8 storage, obs row t at byte t * stride; fields: dict of the [T, n]
+    inputs named actions, values, log_probs, advantages, returns (and starts in env mode), unit
+    stride over envs, any row stride; outs: dict of the contiguous outputs named indices, obs,
+    actions, values, log_probs, advantages, returns (and codes, starts); states: (src, dst)
+    pairs, src f32 [S, n, H] (row 0 is read), dst f32 [B, H].  The tensors are kept alive by the
+    struct."""
+    a = C.PERolloutMb()
+    a.mode, a.T, a.n, a.D, a.B, a.obs_f32 = _MODES[mode], int(T), int(n), int(D), int(B), int(bool(obs_f32))
+    a.seed, a.epoch, a.k = int(seed) & U64, int(epoch) & U64, int(k) & U64
+    a.buf, a.stride, a.buf_bytes = buf.data_ptr(), int(stride), buf.numel() * buf.element_size()
+    keep = [buf, table, ctrl, count]
+    a.table = None if table is None else table.data_ptr()
+    a.ctrl = None if ctrl is None else ctrl.data_ptr()
+    a.count = None if count is None else count.data_ptr()
+    for name in _MB_IN:
+        x = fields.get(name)
+        if x is not None:
+            if tuple(x.shape) != (T, n) or (n > 1 and x.stride(1) != 1):
+                raise ValueError(f"{name} must be [{T}, {n}] with unit stride over envs")
+            setattr(a, name, x.data_ptr())
+            setattr(a, "s_" + name, x.stride(0) if T > 1 else n)
+            keep.append(x)
+    for name in _MB_OUT:
+        x = outs.get(name)
+        if x is not None:
+            if not x.is_contiguous():
+                raise ValueError(f"output {name} must be contiguous")
+            setattr(a, name if name == "indices" else "out_" + name, x.data_ptr())
+            keep.append(x)
+    states = list(states)
+    if len(states) > C.PE_MB_MAX_STATES:
+        raise ValueError(f"at most {C.PE_MB_MAX_STATES} state arrays")
+    a.n_states = len(states)
+    for i, (src, dst) in enumerate(states):
+        a.H = src.shape[-1]
+        if src.dim() != 3 or src.shape[1] != n or tuple(dst.shape) != (B, a.H) or not src.is_contiguous() \
+                or not dst.is_contiguous():
+            raise ValueError(f"states must be contiguous (src [S, {n}, H], dst [{B}, H]) pairs")
+        a.state_src[i], a.state_dst[i] = src.data_ptr(), dst.data_ptr()
+        keep += [src, dst]
+    a._keep = keep
+    return a
+
+
+def minibatch_device(a, device):
+    """pe_internal_rollout_minibatch of a filled pe_rollout_mb, on torch's current stream of `device`."""
+    import ctypes
+    import torch
+    with torch.cuda.device(device):
+        C.check(C.lib().pe_internal_rollout_minibatch(ctypes.byref(a), C.stream_ptr(device)),
+                "pe_internal_rollout_minibatch")
+
+
+class RolloutMinibatch:
+    """One minibatch of a Rollout, named as SB3's RolloutBufferSamples: device tensors owned by the
+    collector, one set per (mode, size), overwritten by the next minibatch of that size.
+
+    Row minibatches: observations f32 [B, D], actions i32 [B], old_values, old_log_prob,
+    advantages, returns f32 [B], indices i32 [B] (the rollout row t * n + env of each sample).
+    Env minibatches: the same time-major, [T, Be(, D)], plus episode_starts u8 [T, Be],
+    env_indices (= indices) i32 [Be] and lstm_states [(h0, c0), ..] f32 [Be, H] per tower (None
+    without a recurrent collector).  codes: the u8 obs rows where obs="codes" asked for them,
+    else None.  count: how many samples (envs) are valid: an int from the generators, which
+    yield views of exactly that many; a device i32 [1] from next_minibatch, whose tensors keep
+    their full size with zeros (indices -1) past count."""
+
+    NAMES = ("observations", "codes", "actions", "old_values", "old_log_prob", "advantages", "returns",
+             "episode_starts")
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def env_indices(self):
+        return self.indices
+
+    def _head(self, count):
+        """Views of the first `count` samples."""
+        ax = (slice(None), slice(0, count)) if self.mode == "envs" else (slice(0, count),)
+        kw = {k: None if getattr(self, k) is None else getattr(self, k)[ax] for k in self.NAMES}
+        states = self.lstm_states and [(h[:count], c[:count]) for h, c in self.lstm_states]
+        return RolloutMinibatch(mode=self.mode, indices=self.indices[:count], lstm_states=states, count=count, **kw)
+
+
 class Rollout:
     """One collect()'s data: device tensors, most of them views of the collector's storage
     (the next collect() overwrites them).
@@ -144,6 +317,43 @@ class Rollout:
         pe_expand_obs_codes launch over the T rows into `out` (or a new tensor).  On a
         float32 batch: a view of the storage where the rows allow one, else one strided copy."""
         return self._c._obs_f32(out)
+
+    def minibatches(self, batch_size=None, epoch=0, seed=0, normalize_advantage=False, obs="f32"):
+        """One epoch of shuffled minibatches (SB3's RolloutBuffer.get): a generator of
+        ceil(T n / batch_size) RolloutMinibatch, which together hold every row of the rollout
+        exactly once, in the order of the keyed permutation rollout_perm(seed, epoch, ..)
+        (host_minibatch_indices gives the same indices without a device).  The last one is short
+        when batch_size does not divide T n; batch_size None: one minibatch of all rows (A2C's
+        get(None)).  Per minibatch one gather kernel reads the collector's storage -- obs codes
+        are decoded on the way, so no [T n, D] float tensor is ever made -- and, with
+        normalize_advantage, the advantages are normalised as PPO.train does ((a - mean) /
+        (std + 1e-8), host_adv_norm bit for bit).  obs="codes" (``obs_codes`` batches) also
+        fills mb.codes.  Current stream, no sync; no allocation after the first call of a size.
+        ValueError for batch_size < 1 or an epoch / seed that is no non-negative int."""
+        return self._c._minibatches("rows", batch_size, epoch, seed, normalize_advantage, obs)
+
+    def env_minibatches(self, envs_per_batch=None, epoch=0, seed=0, normalize_advantage=False, obs="f32"):
+        """One epoch of minibatches of whole sequences, for a recurrent learner: a generator of
+        ceil(n / envs_per_batch) RolloutMinibatch, each the full [T] sequences of envs_per_batch
+        envs drawn by the keyed env permutation, time-major, with episode_starts and -- from a
+        RecurrentRolloutCollector -- the LSTM state (h0, c0) each sequence starts from (raw: the
+        learner applies episode_starts[0] as the collector's forward did).  All sequences have
+        length T, so nothing is padded: this is the project's definition of a recurrent
+        minibatch, not sb3_contrib's split-and-pad sampler.  Otherwise as minibatches()."""
+        return self._c._minibatches("envs", envs_per_batch, epoch, seed, normalize_advantage, obs)
+
+    def next_minibatch(self, batch_size, seed=0, normalize_advantage=False, obs="f32"):
+        """The next row minibatch by the collector's device counters `minibatch_ctrl` = (epoch,
+        next k), which the call advances on the device: k + 1, or (epoch + 1, 0) after an
+        epoch's last minibatch.  The tensors keep their full size (zeros and indices -1 past
+        mb.count, a device i32 [1]).  No host value depends on the counters, so one call can be
+        captured with torch.cuda.graph and every replay yields the following minibatch."""
+        return self._c._next_minibatch(batch_size, seed, normalize_advantage, obs)
+
+    @property
+    def minibatch_ctrl(self):
+        """Device i64 [2] = (epoch, next k) of next_minibatch; set it with copy_ / zero_."""
+        return self._c.minibatch_ctrl
 
 
 class _Collector(Collector):
@@ -193,6 +403,90 @@ class _Collector(Collector):
             values=self.values, log_probs=self.log_probs, advantages=self.advantages, returns=self.returns,
             last_values=self.last_values, last_dones=self._starts_all[T], ep_count=self.ep_count,
             ep_return_sum=self.ep_return_sum, ep_length_sum=self.ep_length_sum)
+
+        # rollout minibatches: the code table on the device (uploaded once), the device counters
+        # of next_minibatch, and the output tensors per (mode, size, codes)
+        self._mb_table = torch.as_tensor(b.code_table(), device=dev) if b.obs_codes else None
+        self.minibatch_ctrl = torch.zeros(2, dtype=torch.int64, device=dev)
+        self._mb_cache = {}
+
+    # ----------------------------------------------------------------- minibatches
+    def _mb(self, mode, B, codes):
+        """The cached RolloutMinibatch (tensors and filled pe_rollout_mb) of a mode and size."""
+        key = (mode, B, codes)
+        mb = self._mb_cache.get(key)
+        if mb is not None:
+            return mb
+        torch, b = self._torch, self.batch
+        T, n, D, dev = self.n_steps, b.num_envs, b.obs_dim, b.device
+        shape = (B,) if mode == "rows" else (T, B)
+        z = lambda sh, dt: torch.zeros(sh, dtype=dt, device=dev)  # noqa: E731
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        states = None
+        lstm = getattr(self, "lstm_states", None) if mode == "envs" else None
+        if lstm is not None:
+            states = [(z((B, h.shape[-1]), f32), z((B, h.shape[-1]), f32)) for h, _ in lstm]
+        mb = RolloutMinibatch(
+            mode=mode, observations=z(shape + (D,), f32), codes=z(shape + (D,), u8) if codes else None,
+            actions=z(shape, i32), old_values=z(shape, f32), old_log_prob=z(shape, f32), advantages=z(shape, f32),
+            returns=z(shape, f32), episode_starts=z(shape, u8) if mode == "envs" else None, indices=z((B,), i32),
+            lstm_states=states, count=z((1,), i32))
+        R = B if mode == "rows" else T * B
+        mb._scratch = z((norm_scratch_len(R),), torch.float64) if norm_scratch_len(R) else None
+        mb._count_dev = mb.count
+        pairs = [] if states is None else [(s, d) for (hs, cs), (hd, cd) in zip(lstm, states) for s, d in ((hs, hd), (cs, cd))]
+        mb._args = mb_args(
+            mode, T, n, D, B, self._buf, self._stride,
+            dict(actions=self.actions, values=self.values, log_probs=self.log_probs, advantages=self.advantages,
+                 returns=self.returns, starts=self._starts_all[:T] if mode == "envs" else None),
+            dict(indices=mb.indices, obs=mb.observations, codes=mb.codes, actions=mb.actions, values=mb.old_values,
+                 log_probs=mb.old_log_prob, advantages=mb.advantages, returns=mb.returns, starts=mb.episode_starts),
+            obs_f32=not b.obs_codes, table=self._mb_table, count=mb.count, states=pairs)
+        self._mb_cache[key] = mb
+        return mb
+
+    def _mb_checks(self, batch_size, seed, obs, M):
+        if obs not in ("f32", "codes"):
+            raise ValueError(f"obs must be 'f32' or 'codes', got {obs!r}")
+        if obs == "codes" and not self.batch.obs_codes:
+            raise ValueError("obs='codes' needs an obs_codes batch")
+        B = M if batch_size is None else check_minibatch_size(batch_size)
+        return B, _uint("seed", seed) & U64
+
+    def _mb_run(self, mb, seed, epoch, k, ctrl, normalize, count):
+        a, dev = mb._args, self.batch.device
+        a.seed, a.epoch, a.k = seed, epoch, k
+        a.ctrl = ctrl.data_ptr() if ctrl is not None else None
+        minibatch_device(a, dev)
+        if not normalize:
+            return
+        adv = mb.advantages
+        if count is None:  # only the device knows it
+            adv_norm_device(adv, count=mb._count_dev, scratch=mb._scratch)
+        else:
+            adv_norm_device(adv[:count] if mb.mode == "rows" else adv[:, :count], scratch=mb._scratch)
+
+    def _minibatches(self, mode, batch_size, epoch, seed, normalize, obs):
+        T, n = self.n_steps, self.batch.num_envs
+        M = T * n if mode == "rows" else n
+        B, seed = self._mb_checks(batch_size, seed, obs, M)
+        epoch = _uint("epoch", epoch) & U64
+        mb = self._mb(mode, B, obs == "codes")
+        C.check(C.lib().pe_internal_rollout_minibatch_check(mb._args), "pe_internal_rollout_minibatch")
+
+        def gen():
+            for k in range(-(-M // B)):
+                count = min(B, M - k * B)
+                self._mb_run(mb, seed, epoch, k, None, normalize, count)
+                yield mb._head(count)
+        return gen()
+
+    def _next_minibatch(self, batch_size, seed, normalize, obs):
+        T, n = self.n_steps, self.batch.num_envs
+        B, seed = self._mb_checks(batch_size, seed, obs, T * n)
+        mb = self._mb("rows", B, obs == "codes")
+        self._mb_run(mb, seed, 0, 0, self.minibatch_ctrl, normalize, None)
+        return mb
 
     def _begin(self):
         """Row 0 of a collect: primed from the batch the first time, else the previous collect's
