@@ -17,24 +17,16 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "csrc", "plantos_batch.hip")
-SRC_HOST = os.path.join(HERE, "csrc", "pe_pystream.cpp")
-SRC_MCTS = os.path.join(HERE, "csrc", "pe_mcts.hip")
-SRC_RENDER = os.path.join(HERE, "csrc", "pe_render.hip")
-SRC_POLICY = os.path.join(HERE, "csrc", "pe_policy.hip")
-SRC_POLICY_HOST = os.path.join(HERE, "csrc", "pe_policy_host.cpp")
-SRC_POLICY_LSTM = os.path.join(HERE, "csrc", "pe_policy_lstm.hip")
-SRC_POLICY_BF16 = os.path.join(HERE, "csrc", "pe_policy_bf16.hip")
-SRC_ROLLOUT = os.path.join(HERE, "csrc", "pe_rollout.hip")
-SRC_ROLLOUT_HOST = os.path.join(HERE, "csrc", "pe_rollout_host.cpp")
-SRC_REPLAY = os.path.join(HERE, "csrc", "pe_replay.hip")
-SRC_REPLAY_HOST = os.path.join(HERE, "csrc", "pe_replay_host.cpp")
-SOURCES = [SRC, SRC_MCTS, SRC_RENDER, SRC_HOST, SRC_POLICY, SRC_POLICY_HOST, SRC_POLICY_LSTM, SRC_ROLLOUT,
-           SRC_ROLLOUT_HOST, SRC_REPLAY, SRC_REPLAY_HOST, SRC_POLICY_BF16]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in
-                  ("pe_device.hpp", "pe_fast.hpp", "pe_quad.hpp", "pe_coop.hpp", "pe_handle.hpp", "pe_far.hpp",
-                   "pe_plan.hpp", "pe_host.hpp", "pe_policy_math.hpp", "pe_policy_impl.hpp", "pe_policy_plan.hpp",
-                   "pe_rollout_math.hpp", "pe_rollout_minibatch.h", "pe_replay_math.hpp")] + [
+CSRC = os.path.join(HERE, "csrc")
+# The translation units, in link order (the library's bytes depend on it).
+SOURCES = [os.path.join(CSRC, f) for f in
+           ("plantos_batch.hip", "pe_mcts.hip", "pe_render.hip", "pe_pystream.cpp", "pe_policy.hip",
+            "pe_policy_host.cpp", "pe_policy_lstm.hip", "pe_rollout.hip", "pe_rollout_host.cpp", "pe_replay.hip",
+            "pe_replay_host.cpp", "pe_policy_bf16.hip")]
+# What a rebuild depends on, by rule: every header beside the sources (lidar_tables.inc, which
+# build() regenerates first, by name too), the C API and the generator of the LIDAR tables.
+DEPS = SOURCES + [os.path.join(CSRC, f) for f in
+                  sorted({f for f in os.listdir(CSRC) if f.endswith((".hpp", ".h", ".inc"))} | {"lidar_tables.inc"})] + [
     os.path.join(REPO, "include", "plantos_batch.h"), os.path.join(HERE, "tools_gen_lidar.py")]
 OUT = os.path.join(HERE, "plantos_amd", "libplantos_hip.so")
 OBJ_DIR = os.path.join(REPO, "build", "obj")
@@ -44,7 +36,7 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
 # Flags of single sources.  pe_rollout.hip: the SLP vectoriser packs two multiplies of the GAE
 # chain into one v_pk_mul_f32 whose unused half is a register of the window still being
 # loaded, and the wait that costs serialises the scan with the loads it should overlap.
-SOURCE_FLAGS = {SRC_ROLLOUT: ["-fno-slp-vectorize"]}
+SOURCE_FLAGS = {os.path.join(CSRC, "pe_rollout.hip"): ["-fno-slp-vectorize"]}
 
 
 def build(force=False, verbose=False, out=OUT, extra_flags=(), obj_dir=None):
@@ -56,8 +48,7 @@ def build(force=False, verbose=False, out=OUT, extra_flags=(), obj_dir=None):
     missing = [d for d in DEPS if not os.path.exists(d)]
     if missing:
         raise FileNotFoundError(f"build dependencies missing: {missing}")
-    deps = DEPS + [os.path.join(HERE, "csrc", "lidar_tables.inc")]
-    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in DEPS):
         return out
     if obj_dir is None:
         key = hashlib.sha256(repr((sorted(extra_flags), os.path.abspath(out))).encode()).hexdigest()[:12]

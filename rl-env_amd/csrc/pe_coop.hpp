@@ -1,7 +1,7 @@
 // pe_coop.hpp -- wave-cooperative auto-reset: one env's reset() by all 64 lanes.
 //
 // The lane-per-env reset (gen_map + build_obs_fresh in pe_device.hpp /
-// plantos_batch.hip) is a serial chain of ~60k instructions per env: scans of
+// pe_obs.hpp) is a serial chain of ~60k instructions per env: scans of
 // the grid image per plant pick, rejection loops, per-lane row stores.  That is
 // fine when every lane of the commit wave has an env to reset (a synchronized
 // batch truncating together), but inside a step it is the whole block's latency:
@@ -780,8 +780,8 @@ __device__ __forceinline__ CodeLd obs_code_loads(const Tables* tab, int R, int G
 __device__ __forceinline__ void ctab_from_lds(const float* smem, float* ctab, int R, int G, int c, int onehot_zero) {
   const int f = c <= R + 1 ? c
                            : ((c >= kCodeVis && c < kCodeVis + 16)
-                                  ? 328 + (c - kCodeVis)
-                                  : ((c >= kCodePos && c < kCodePos + G) ? 72 + (c - kCodePos) : onehot_zero));
+                                  ? kTabVis + (c - kCodeVis)
+                                  : ((c >= kCodePos && c < kCodePos + G) ? kTabPos + (c - kCodePos) : onehot_zero));
   ctab[c] = smem[f];
 }
 

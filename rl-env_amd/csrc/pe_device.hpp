@@ -39,6 +39,7 @@
 //   w2 = collisions | flags<<16     w3 = episode (resets so far)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace pe {
@@ -78,6 +79,31 @@ struct Tables {
   uint64_t grid_real[kMaxWPR]; // low-bit mask of the G real columns
   uint32_t vis_pad[kMaxNW];    // empty visit row: nibble 10 in the 4 pad columns
 };
+
+// Every env kernel copies Tables (or its head) to the start of its LDS; the tables there, as
+// float offsets.  Derived from the struct: a change to Tables moves them or fails the build.
+constexpr int kTabDist = (int)(offsetof(Tables, dist) / sizeof(float));
+constexpr int kTabPos = (int)(offsetof(Tables, pos) / sizeof(float));
+constexpr int kTabVis = (int)(offsetof(Tables, vis) / sizeof(float));
+constexpr int kTabPads = (int)(offsetof(Tables, grid_pad) / sizeof(float));  // the pad masks, to the struct's end
+static_assert(kTabDist == 0 && kTabPos == 72 && kTabVis == 328 && kTabPads == 344, "LDS map of the tables");
+
+// The sector kernels (pe_step_quad, pe_step_far) read dist[0..RM+1] of the LDS copy (RM: their
+// largest R; dist[R+1] = 1.0, nothing hit) and park words of their own in the floats above:
+//
+//   dist[ 0 .. RM+1]   the ray distances
+//   dist[24 .. 28]     kInfoParkF: the one done env's post-step scalars + wfix, commit wave -> info
+//                      wave (el_info_hit; kernels with an info wave only, which keep RM + 2 <= 24)
+//   dist[48 .. 63]     kOneHotF: the one-hot rows of the 4 entity codes as float4 (pe_quad.hpp)
+//   dist[70 .. 71]     kDoneMaskF: the block's done mask, one u64 (word kDoneMask64 of the LDS)
+constexpr int kInfoParkF = 24, kInfoParkN = 5;
+constexpr int kOneHotF = 48, kOneHotN = 16;
+constexpr int kDoneMaskF = 70, kDoneMask64 = kDoneMaskF / 2;
+static_assert(kInfoParkF + kInfoParkN <= kOneHotF && kOneHotF % 4 == 0 && kOneHotF + kOneHotN <= kDoneMaskF &&
+                  kDoneMaskF % 2 == 0 && kDoneMaskF + 2 <= kTabPos,
+              "parked words inside dist[], apart from each other");
+// a kernel of largest range RM keeps its ray distances below the words it parks (info: it has an info wave)
+constexpr bool dist_park_ok(int RM, bool info) { return RM + 2 <= (info ? kInfoParkF : kOneHotF); }
 
 // Batched CurriculumWrapper state per env (A2C_training.py:41-54), when enabled.
 struct CurRec {

@@ -1,7 +1,8 @@
 // pe_far.hpp -- the sector step kernel for long LIDAR ranges: pe_step_far<C, R>
 // (compile-time C, R with C % 4 == 0 and 15 <= R <= 32, e.g. SURVEY §8(d)'s 64x64 /
-// 64 rays / R = 32 stress variant).  Included by plantos_batch.hip after pe_step_quad,
-// whose auto-reset slow path and tile stores it shares.
+// 64 rays / R = 32 stress variant).  Included by plantos_batch.hip after
+// pe_step_quad.hpp; it shares that kernel's auto-reset slow path (pe_quad_done.hpp) and tile
+// stores (pe_tile.hpp).
 //
 // The sector kernel's LDS window ([2R+3 rows][64 envs] of one funnel-shifted word) does
 // not reach R > 14, and a (2R+1)^2 window of 64 envs does not fit LDS.  Here every
@@ -31,7 +32,7 @@
 // byte tile (~34 KB at 64x64 / 64 rays), so the 1024 workgroups of a 65536-env batch
 // are resident at once (4 per CU); the cost that remains is the grid rows
 // (~2 KB per env-step with the 2R pad) and the obs stream.
-// (a fragment of plantos_batch.hip's anonymous namespace)
+// (a fragment of plantos_batch.hip's anonymous namespace; include after pe_step_quad.hpp)
 #pragma once
 
 constexpr int kFarWaves = 4;
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
   constexpr int NW = kFarWaves, LS = kQuadEnvs, CW = NW - 1, D = 5 * C + 27;
   static_assert(C % 4 == 0 && C >= 4, "quadrant sectors");
   static_assert(R >= 2 && R <= 32, "64-bit packed probe codes");
-  static_assert(R + 2 <= kOneHotF, "ray tables inside dist[]");
+  static_assert(dist_park_ok(R, false), "ray tables inside dist[]");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const Geo& g = a.g;
   const State& st = a.st;
@@ -469,14 +470,14 @@ __global__ __launch_bounds__(64 * kFarWaves, 4) void pe_step_far(StepArgs a) {
       default: far_sector<C, R, 3>(gb32, g.G, xp, yp, watered, row); break;
     }
   }
-  // ---- DummyVecEnv auto-reset (rare): the commit wave's done mask in dist[70..71]
+  // ---- DummyVecEnv auto-reset (rare): the commit wave's done mask at kDoneMaskF
   if (wv == CW) {
     const uint64_t dm = __ballot(done);
-    if (lane == 0) reinterpret_cast<uint64_t*>(smem)[35] = dm;
+    if (lane == 0) reinterpret_cast<uint64_t*>(smem)[kDoneMask64] = dm;
   }
   // the block barrier without a memory fence (see pe_step_quad)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  const uint64_t dmask = reinterpret_cast<const uint64_t*>(smem)[35];
+  const uint64_t dmask = reinterpret_cast<const uint64_t*>(smem)[kDoneMask64];
   const uint64_t dmu = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)dmask) |
                        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(dmask >> 32)) << 32);
   const bool any_done = dmu != 0ull;

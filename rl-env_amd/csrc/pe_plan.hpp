@@ -1,5 +1,5 @@
 // pe_plan.hpp -- the device-free half of handle creation (a part of plantos_batch.hip, included
-// after the kernels: it reads their limits and LDS layouts).
+// after the kernels' headers: it reads their limits and LDS layouts).
 //
 // make_plan() decides everything pe_create decides before its first allocation -- geometry,
 // rules, the step kernel, its workgroup shape, the reset paths, the ray-table format and the

@@ -64,8 +64,7 @@ __device__ __forceinline__ uint64_t quad_row(const uint64_t* gb, const Geo& g, i
 
 // LDS table words the sector rays read (in the tables' dist[] region, which holds
 // dist[0..R]): dist[R+1] = 1.0 (nothing hit), and at kOneHotF the one-hot rows of
-// the 4 entity codes as float4 (16-B aligned).
-constexpr int kOneHotF = 48;
+// the 4 entity codes as float4 (16-B aligned).  kOneHotF: pe_device.hpp, the map of dist[].
 
 // Rays [W*C/NW, (W+1)*C/NW) of one env (the sector of wave W): first hit over the
 // post-move window rows read from LDS (row k of the [row][env] block = grid row

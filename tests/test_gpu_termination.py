@@ -7,8 +7,8 @@ move into it) beside, below, between and on envs that are about to truncate, und
 `adv` rewards with max_steps = 50.  T: an env made to terminate; P: an env whose step
 counter is set to 49, so it truncates in the event step and the kernel can know it.
 
-What the code does with each scenario (plantos_batch.hip pe_step_quad / quad_done_path,
-pe_far.hpp; the tests cannot observe which path a block took, this is read from the code):
+What the code does with each scenario (pe_step_quad.hpp pe_step_quad, pe_quad_done.hpp
+quad_done_path, pe_far.hpp; the tests cannot observe which path a block took, this is read from the code):
 
   the prediction   pm = __ballot(s.step + 1 >= rl.max_steps); npred (npk) = popcount(pm);
                    ndone = popcount(ballot(terminated || truncated)) after the transition.

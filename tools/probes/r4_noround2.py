@@ -1,7 +1,7 @@
 # Timing probe (wrong results): the one-word sector kernel's visit-row loads made
 # independent of the loader env's position (fixed rows 0..6 of slot 0), so that hipcc
 # issues them with round 1 -- what the step costs with no dependent second round.
-p = "rl-env_amd/csrc/plantos_batch.hip"
+p = "rl-env_amd/csrc/pe_step_quad.hpp"
 s = open(p).read()
 old = """      const uint32_t* lvb = vis_env(st, g, el, lw.w);  // (lw.w: the loader env's episode)
       {

@@ -2,7 +2,7 @@
 # position, so hipcc issues them with round 1), and the LDS visit rows forced to a
 # visit count of 1 in every cell (the loaded bits kept live through an OR of bit 0),
 # so that no env explores or terminates: the same resets as the real kernel.
-p = "rl-env_amd/csrc/plantos_batch.hip"
+p = "rl-env_amd/csrc/pe_step_quad.hpp"
 s = open(p).read()
 old = """      const uint32_t* lvb = vis_env(st, g, el, lw.w);  // (lw.w: the loader env's episode)
       {

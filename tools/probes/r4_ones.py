@@ -1,6 +1,6 @@
 # Timing probe (wrong results), the control of r4_noround2b.py: the real dependent
 # round 2, the LDS visit rows forced to a visit count of 1 in every cell.
-p = "rl-env_amd/csrc/plantos_batch.hip"
+p = "rl-env_amd/csrc/pe_step_quad.hpp"
 s = open(p).read()
 old2 = """          lvis[k * LS + le] = vo ? ((lo >> vo) | (hi << (32 - vo))) : lo;
         }
