@@ -255,7 +255,11 @@ int pe_pystream_destroy(pe_pystream* s);
  * best_action (:62-69) are the reference's, bit for bit.  Sim envs water with the
  * fork's semantics (hydrated plant: R_MISTAKE).  Searches read the live state of
  * `h` and never modify it; they step nothing: apply the actions with pe_step.
- * Scratch: (G*G + 2*max_depth + 2) * 4 + (n_simulations + 1) * 32 + 2504 bytes/env. */
+ * Scratch, bytes per env (one allocation per handle, every array rounded up to 256 B, plus
+ * (n_simulations + 1) * 8 per handle): G*G * 4 + (n_simulations + 1) * 32 + 2512 for the
+ * clone, the tree and the stream, and the arrays of the handle's own search kernel
+ * (pe_mcts_kernel_name) only: (max_depth + 4) * 8 under pe_mcts_search_kernel,
+ * G*G rounded up to 16, + G*G * 8 under pe_mcts_search_lds_kernel. */
 typedef struct pe_mcts pe_mcts;
 int pe_mcts_create(pe_handle* h, int32_t n_simulations, double c_param, int32_t max_depth, pe_mcts** out);
 /* Every pe_mcts_* call needs `h` alive, except pe_mcts_destroy, which may follow pe_destroy(h). */

@@ -83,5 +83,24 @@ extern "C" int pe_internal_policy_plan_prec(int32_t D, int32_t n_envs, int32_t n
                                             const pe_policy_lstm* lstms, const pe_policy_tower* shapes,
                                             int32_t activation, int32_t env_tile, int32_t precision,
                                             pe_policy_plan_info* out);
+// pe_internal_mcts_plan (pe_mcts.hip): what pe_mcts_create would decide for a handle of grid side
+// G and n_envs envs, before it touches a device (pe_mcts_plan.hpp) -- no HIP call.  On rejection
+// pe_mcts_create's error code, with pe_last_error() set.
+struct pe_mcts_plan_info {
+  int32_t kernel;      // 1: pe_mcts_search_lds_kernel, 0: pe_mcts_search_kernel
+  int32_t ldsp, ggp;   // LDS / global per-env byte strides of the clone bytes
+  uint32_t clone_blocks, search_blocks;
+  uint64_t lds_bytes;  // dynamic LDS of a workgroup of the LDS kernel (whichever kernel runs)
+  // cellw, ulog, nodes, rng, logt, cellb, csim, csg: bytes from the start of the handle's one
+  // allocation; size 0: not allocated (the kernel reads no such array)
+  uint64_t offset[8], size[8];
+  uint64_t total;
+};
+extern "C" int pe_internal_mcts_plan(int32_t G, int32_t n_envs, int32_t n_simulations, int32_t max_depth,
+                                     pe_mcts_plan_info* out);
+// One np.random stream between numpy's (key u32[624], pos in [0, 624]) and the device form
+// (u32[628], pe_mcts_rng.hpp), as pe_mcts_set_rng / pe_mcts_get_rng convert it.  Host arrays; no device.
+extern "C" int pe_internal_mcts_rng_to_device_host(const uint32_t* key, int32_t pos, uint32_t* dev);
+extern "C" int pe_internal_mcts_rng_from_device_host(const uint32_t* dev, uint32_t* key, int32_t* pos);
 // pe_internal_render_free (pe_render.hip): frees the handle's render tables (pe_destroy).
 extern "C" void pe_internal_render_free(pe_handle* h);

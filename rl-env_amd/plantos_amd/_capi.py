@@ -84,6 +84,23 @@ class PEPolicyPlanInfo(ctypes.Structure):
                 ("state_floats", ctypes.c_uint64)]
 
 
+MCTS_ARRAYS = ("cellw", "ulog", "nodes", "rng", "logt", "cellb", "csim", "csg")
+MCTS_RNG_WORDS = 628  # one stream in device form: mt[624], pos, saved mt[0], 2 pad
+
+
+class PEMctsPlanInfo(ctypes.Structure):
+    """pe_mcts_plan_info (csrc/pe_handle.hpp): what pe_mcts_create would decide, without a device.
+    offset / size: the arrays of MCTS_ARRAYS in the handle's one allocation (size 0: not allocated)."""
+    _fields_ = [("kernel", ctypes.c_int32), ("ldsp", ctypes.c_int32), ("ggp", ctypes.c_int32),
+                ("clone_blocks", ctypes.c_uint32), ("search_blocks", ctypes.c_uint32),
+                ("lds_bytes", ctypes.c_uint64), ("offset", ctypes.c_uint64 * 8), ("size", ctypes.c_uint64 * 8),
+                ("total", ctypes.c_uint64)]
+
+    @property
+    def kernel_name(self):
+        return "pe_mcts_search_lds_kernel" if self.kernel else "pe_mcts_search_kernel"
+
+
 PE_MB_ROWS, PE_MB_ENVS = 0, 1
 PE_MB_MAX_STATES = 4
 
@@ -196,6 +213,9 @@ def _signatures():
         "pe_internal_plan": (INT, [CP, I32, I32, ctypes.POINTER(PEPlanInfo)]),
         "pe_internal_policy_plan": (INT, plan + [ctypes.POINTER(PEPolicyPlanInfo)]),
         "pe_internal_policy_plan_prec": (INT, plan + [I32, ctypes.POINTER(PEPolicyPlanInfo)]),
+        "pe_internal_mcts_plan": (INT, [I32, I32, I32, I32, ctypes.POINTER(PEMctsPlanInfo)]),
+        "pe_internal_mcts_rng_to_device_host": (INT, [P, I32, P]),
+        "pe_internal_mcts_rng_from_device_host": (INT, [P, P, P]),
         # csrc/pe_rollout_minibatch.h
         "pe_internal_rollout_minibatch_check": (INT, [ctypes.POINTER(PERolloutMb)]),
         "pe_internal_rollout_minibatch": (INT, [ctypes.POINTER(PERolloutMb), P]),
@@ -208,7 +228,8 @@ def _signatures():
 
 # name -> (restype, [argtypes]).  SIGNATURES: every function of include/plantos_batch.h
 # (tests/test_capi_symbols.py checks each entry against the header's prototype);
-# INTERNAL_SIGNATURES: the plan entry points of csrc/pe_handle.hpp and the rollout minibatches of
+# INTERNAL_SIGNATURES: the plan entry points of csrc/pe_handle.hpp (with the MCTS stream
+# conversions declared beside pe_internal_mcts_plan) and the rollout minibatches of
 # csrc/pe_rollout_minibatch.h, which are not part of the ABI.
 SIGNATURES, INTERNAL_SIGNATURES = _signatures()
 EXPORTS = list(SIGNATURES)
@@ -297,6 +318,36 @@ def policy_plan(obs_dim, n_envs, num_cus, lstms, shapes, activation, env_tile=0,
                                         int(activation), int(env_tile), ctypes.byref(info)),
           "pe_policy_create" if lstms is None else "pe_policy_create_lstm")
     return info
+
+
+def mcts_plan(grid_size, n_envs, n_simulations, max_depth):
+    """pe_internal_mcts_plan: the search kernel, its LDS and grids and the layout of the allocation
+    pe_mcts_create would choose over a batch of `n_envs` envs of grid side `grid_size`.  Needs no
+    device; raises as pe_mcts_create does."""
+    info = PEMctsPlanInfo()
+    check(lib().pe_internal_mcts_plan(int(grid_size), int(n_envs), int(n_simulations), int(max_depth),
+                                      ctypes.byref(info)), "pe_mcts_create")
+    return info
+
+
+def mcts_rng_to_device(key, pos):
+    """One np.random stream, numpy's (key uint32 [624], pos) -> the device form uint32 [628], as
+    pe_mcts_set_rng stores it (and refuses it).  Host only."""
+    import numpy as np
+    key = np.ascontiguousarray(key, np.uint32).reshape(624)
+    dev = np.zeros(MCTS_RNG_WORDS, np.uint32)
+    check(lib().pe_internal_mcts_rng_to_device_host(ptr(key), int(pos), ptr(dev)), "pe_mcts_set_rng")
+    return dev
+
+
+def mcts_rng_from_device(dev):
+    """The device form uint32 [628] -> numpy's (key uint32 [624], pos), as pe_mcts_get_rng reports it.
+    Host only."""
+    import numpy as np
+    dev = np.ascontiguousarray(dev, np.uint32).reshape(MCTS_RNG_WORDS)
+    key, pos = np.zeros(624, np.uint32), ctypes.c_int32()
+    check(lib().pe_internal_mcts_rng_from_device_host(ptr(dev), ptr(key), ctypes.byref(pos)), "pe_mcts_get_rng")
+    return key, pos.value
 
 
 def default_config(grid_size, num_plants, num_obstacles, lidar_range, lidar_channels):

@@ -5,7 +5,7 @@ the host test (test_mcts_cases.py) can show with the oracle alone that each case
 code path it is there for, and the GPU test asserts the same conditions on the searches it
 compares.
 
-Which search kernel runs (pe_mcts.hip, pe_mcts_kernel_name): the LDS kernel keeps, per workgroup
+Which search kernel runs (pe_mcts_plan.hpp, pe_mcts_kernel_name): the LDS kernel keeps, per workgroup
 of 64 envs, each env's cells as bytes -- G*G rounded up to whole dwords, plus one dword when that
 count is even (odd stride between lanes) -- and a ring of 32 draws (128 B); it runs when G <= 64
 and the 64 envs fit 64 KiB, which holds up to G = 29 (62208 B; G = 30 needs 65792 B).

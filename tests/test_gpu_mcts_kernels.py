@@ -206,6 +206,24 @@ def test_create_limits():
         b.close()
 
 
+@pytest.mark.parametrize("geom", MC.DEGENERATE_GEOMS, ids=[MC.case_id(MC.case(g)) for g in MC.DEGENERATE_GEOMS])
+def test_kernel_name_is_the_plans(geom):
+    """the kernel a handle reports is the one the device-free plan (tests/test_mcts_plan_host.py)
+    names for its grid side, env count and budget: g7 the LDS kernel, G30 the global one"""
+    from plantos_amd import _capi as C
+    from plantos_amd.mcts import MCTS
+    cs = MC.case(geom)
+    b = U.make_batch(cs["cfg"], MC.N, MC.SEED, 1000, 0.7, U.PRESETS["default"])
+    try:
+        m = MCTS(b, n_simulations=cs["n_sims"], max_depth=cs["depth"])
+        try:
+            assert m.kernel_name == C.mcts_plan(cs["cfg"][0], MC.N, cs["n_sims"], cs["depth"]).kernel_name == cs["kernel"]
+        finally:
+            m.close()
+    finally:
+        b.close()
+
+
 def test_mcts_may_be_closed_after_its_batch():
     """pe_mcts_destroy needs nothing of the env handle (a collector may finalize a batch before the
     MCTS over it): closing in that order succeeds and leaves no HIP error behind."""
