@@ -47,8 +47,8 @@ class CurriculumTwin:
     CPython stream of the reference's fixtures."""
 
     def __init__(self, cfg, n, seed, stream="philox", max_steps=None, initial=40.0, maximum=100.0, inc=10.0,
-                 max_eps=3, terminate=True):
-        self.c = O.config(*cfg)
+                 max_eps=3, terminate=True, map_algo=0):
+        self.c = O.config(*cfg, map_algo=map_algo)
         if max_steps is not None:
             self.c.max_steps = max_steps
         self.b = O.Batch(self.c, n)

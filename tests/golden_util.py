@@ -5,8 +5,8 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-INJECT_CFGS = ["g20", "g21", "g25", "g64", "g64r32", "g7", "g32"]
-MAP_CFGS = ["g20", "g21", "g25", "g64", "g7", "g32"]
+INJECT_CFGS = ["g20", "g21", "g25", "g64", "g64r32", "g7", "g32", "g128", "g128r64"]
+MAP_CFGS = ["g20", "g21", "g25", "g64", "g7", "g32", "g128"]
 TRAJ_FILES = ["traj_g20_random", "traj_g20_explore", "traj_g7_explore", "traj_g21_explore"]
 
 

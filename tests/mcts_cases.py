@@ -37,23 +37,25 @@ GEOM = {
     "g7": (7, 3, 3, 3, 12), "g20": (20, 10, 12, 6, 16),
     "G28": (28, 10, 12, 6, 16), "G29": (29, 10, 12, 6, 16), "G30": (30, 10, 12, 6, 16), "G32": (32, 10, 12, 6, 16),
     "g32": (32, 20, 30, 9, 24), "g40": (40, 30, 40, 8, 48), "g64": (64, 100, 120, 6, 64),
+    "G100": (100, 20, 30, 6, 16),
 }
 # written out, not derived: a drift of the rule in expected_kernel() or in the library shows here
 KERNEL = {"g7": LDS_KERNEL, "g20": LDS_KERNEL, "G28": LDS_KERNEL, "G29": LDS_KERNEL, "G30": GLOBAL_KERNEL,
-          "G32": GLOBAL_KERNEL, "g32": GLOBAL_KERNEL, "g40": GLOBAL_KERNEL, "g64": GLOBAL_KERNEL}
+          "G32": GLOBAL_KERNEL, "g32": GLOBAL_KERNEL, "g40": GLOBAL_KERNEL, "g64": GLOBAL_KERNEL,
+          "G100": GLOBAL_KERNEL}
 
 
-def case(geom, n_sims=20, depth=40, c=1.414, rules="default", max_steps=1000, p=0.7, edit=None, mseed=41):
+def case(geom, n_sims=20, depth=40, c=1.414, rules="default", max_steps=1000, p=0.7, edit=None, mseed=41, n=N):
     return dict(geom=geom, cfg=GEOM[geom], kernel=KERNEL[geom], n_sims=n_sims, depth=depth, c=c, rules=rules,
-                max_steps=max_steps, p=p, edit=edit, mseed=mseed)
+                max_steps=max_steps, p=p, edit=edit, mseed=mseed, n=n)
 
 
 def host_side(cs):
     """(twin, snapshot before the edits): the oracle's envs after WARM synthetic steps -- the state
     the GPU batch must be in after the same steps -- then the case's edits of that state."""
-    tw = U.Twin(cs["cfg"], N, SEED, cs["max_steps"], cs["p"], U.PRESETS[cs["rules"]])
+    tw = U.Twin(cs["cfg"], cs["n"], SEED, cs["max_steps"], cs["p"], U.PRESETS[cs["rules"]])
     for t in range(WARM):
-        tw.step(U.host_synth(N, t))
+        tw.step(U.host_synth(cs["n"], t))
     before = U.snapshot(tw.ov)
     if cs["edit"] is not None:
         cs["edit"](tw.ov)
@@ -153,6 +155,8 @@ CHAIN = case("g32")
 DEEP_SIMS = 400
 DEEP = [case(g, n_sims=DEEP_SIMS, depth=30, c=0.0) for g in ("g20", "g32")]
 SATURATION = [case(g, n_sims=30, edit=saturate) for g in ("g20", "G29", "G32")]
+# the global kernel is documented for any G: a grid side above 64 (16 envs, a small budget)
+ABOVE_64 = case("G100", n_sims=8, depth=10, n=16)
 DEGENERATE_GEOMS = ("g7", "G30")
 DEGENERATE_BUDGETS = [(s, d) for s in (0, 1, 4, 5, 6, 40) for d in (0, 1, 2)]
 

@@ -104,9 +104,10 @@ class Twin:
     host draw is below 0.5), every output a GPU step has to reproduce, and the bookkeeping for
     the conditions on the inputs (which rewards occurred, which plants were watered)."""
 
-    def __init__(self, cfg, n, seed, max_steps, p, rules, water_seed=9):
+    def __init__(self, cfg, n, seed, max_steps, p, rules, water_seed=9, map_algo=0):
         self.cfg, self.n, self.seed, self.max_steps, self.p, self.rules = cfg, n, seed, max_steps, p, rules
-        self.ov = OracleVec(cfg, np.arange(n), seed, max_steps=max_steps, thirsty_plant_prob=p, **rules)
+        self.ov = OracleVec(cfg, np.arange(n), seed, max_steps=max_steps, map_algo=map_algo, thirsty_plant_prob=p,
+                            **rules)
         self.wrng = np.random.default_rng(water_seed)
         self.seen = set()       # f64 step rewards that occurred
         self.watered = np.zeros((n, cfg[0], cfg[0]), bool)  # plants watered in the current episode

@@ -50,14 +50,26 @@ def test_device_maze_reset_matches_oracle(name):
     b.close()
 
 
+SPREAD = {"g64": 40}  # env e starts at step 999 - k(e), k in [0, 40): a short window holds every env's reset
+
+
 @pytest.mark.parametrize("name,n,steps", [("g20", 2048, 1050), ("g7fallback", 300, 1010), ("g64", 128, 60)])
 def test_maze_rollout_parity(name, n, steps):
     """Auto-reset inside the step kernel generates mazes (the 1000-step truncation
-    is crossed): every output of every step vs the oracle."""
+    is crossed): every output of every step vs the oracle, the terminal outputs of the
+    done envs included, then the whole state.  g64 is desynchronized (SPREAD): its 64x64
+    mazes are generated a few envs at a time."""
     cfg = CFG[name]
     seed = 31
+    spread = SPREAD.get(name)
     b = make(cfg, n, seed=seed)
     ov = OracleVec(cfg, np.arange(n), seed, map_algo=1)
+    if spread is not None:
+        start = (999 - np.random.default_rng(3).integers(0, spread, n)).astype(np.int32)
+        sc = np_(b.get_state(parts=("scalars",))["scalars"])
+        sc[:, O.S_STEP] = start
+        b.set_state(scalars=sc)
+        ov.b.scal[:, O.S_STEP] = start
     act = torch.empty(n, dtype=torch.int32, device="cuda:0")
     for t in range(steps):
         b.synth_actions(seed, t, out=act)
@@ -66,8 +78,16 @@ def test_maze_rollout_parity(name, n, steps):
         assert (np_(rew) == o_rew.astype(np.float32)).all(), t
         assert (np_(te).astype(bool) == o_te).all() and (np_(tr).astype(bool) == o_tr).all(), t
         assert (np_(obs) == o_obs).all(), t
+        done = o_te | o_tr
+        if done.any():
+            assert (np_(b.terminal_obs)[done] == o_tobs[done]).all(), t
+            assert (np_(b.episode_return)[done] == o_ret[done]).all(), t
+            assert (np_(b.episode_length)[done] == o_len[done]).all(), t
+    assert ov.b.scal[:, O.S_EPISODE].min() >= 2  # every env was reset in the window
     st = b.get_state()
     assert (np_(st["cells"]) == ov.b.cells).all()
+    assert (np_(st["visits"]) == ov.b.visits).all()
+    assert (np_(st["explored"]) == ov.b.explored).all()
     assert (np_(st["scalars"]) == ov.b.scal).all()
     b.close()
 

@@ -34,7 +34,7 @@ def gpu_side(cs, tw, before):
     """the GPU batch of a case: the same WARM synthetic steps as the oracle twin took, then the
     oracle's (edited) state pushed over it -- U.push first checks that the batch's own state
     equals the twin's before the edits"""
-    n = MC.N
+    n = cs["n"]
     b = U.make_batch(cs["cfg"], n, MC.SEED, cs["max_steps"], cs["p"], U.PRESETS[cs["rules"]])
     acts = torch.empty(n, dtype=torch.int32, device="cuda:0")
     for t in range(MC.WARM):
@@ -113,6 +113,14 @@ def test_global_kernel_large_geometries(cs):
     with open_case(cs) as (tw, b, m):
         st = search_and_compare(m, b, tw.ov, MC.streams(cs["mseed"]), cs["geom"])
     MC.large_conditions(st)
+
+
+def test_global_kernel_above_64():
+    """G = 100 (10000 cells per sim env, 4 row words): pe_mcts_search_kernel takes any grid side"""
+    cs = MC.ABOVE_64
+    with open_case(cs) as (tw, b, m):
+        assert m.kernel_name == MC.GLOBAL_KERNEL and b.grid_size == 100
+        search_and_compare(m, b, tw.ov, MC.streams(cs["mseed"], cs["n"]), cs["geom"])
 
 
 def test_global_kernel_masked_and_chained():

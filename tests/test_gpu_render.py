@@ -82,6 +82,7 @@ STEPPED = {
     "g32": ((32, 20, 30, 9, 24), 3),
     "g64": ((64, 100, 120, 6, 64), 4),
     "g64r32": ((64, 100, 120, 32, 64), 2),
+    "g128": ((128, 10, 12, 6, 16), 2),  # the largest grid side: frames of 256 x 256
 }
 
 
@@ -208,6 +209,24 @@ def test_render_leaves_state_and_next_step_unchanged():
         assert np.array_equal(sa[k], stw[k]), k
     a.close()
     twin.close()
+
+
+def test_width_limit_at_the_largest_grid():
+    """grid_size * cell_size <= 4096: at G = 128 cell_size 32 is the last one drawn, 33 is rejected
+    and draws nothing"""
+    cfg, _ = STEPPED["g128"]
+    b = make(cfg, 2, seed=3)
+    st = state(b)
+    assert np.array_equal(np_(b.render([1], cell_size=32)), ref(b, st, [1], 32))
+    out = torch.full((1, 8, 8, 3), 0xCD, dtype=torch.uint8, device=DEV)
+    with pytest.raises(ValueError, match=r"grid_size \* cell_size <= 4096"):
+        b.render([1], cell_size=33)
+    from plantos_amd import _capi
+    assert _capi.lib().pe_render(b.handle, 1, None, 33, ctypes.c_void_p(out.data_ptr()), 3 * 4224 * 4224, 3 * 4224,
+                                 b._stream()) == _capi.PE_ERR_ARG
+    torch.cuda.synchronize()
+    assert (np_(out) == 0xCD).all()  # nothing was launched
+    b.close()
 
 
 # ------------------------------------------------------------------ arguments

@@ -20,6 +20,8 @@ Fixtures written (all under tests/golden/):
                          (A2C_training.py:216-218 semantics, SB3 step_wait)
   traj_g12r2_rules.npz   the same under non-default rewards and thirsty_plant_prob
                          (`python tools/gen_golden.py rules`)
+  inject_g128[r64].npz,  the same kinds at grid_size 128, the top of the accepted domain
+  maps_g128, maze_g128   (`python tools/gen_golden.py domain`)
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py
 """
@@ -53,6 +55,8 @@ CONFIGS = {
     "g64r32": (64, 100, 120, 32, 64),
     "g7": (7, 3, 3, 3, 12),          # tiny grid: rays leave the map
     "g32": (32, 20, 30, 9, 24),
+    "g128": (128, 10, 12, 6, 16),    # the largest grid side: 5 row words at R = 6
+    "g128r64": (128, 20, 30, 64, 16),  # ... and the longest range: G + 2R = 256, 8 row words
 }
 
 EMPTY, OBST, HYD, THIRSTY = 0, 1, 2, 3
@@ -720,6 +724,21 @@ def main_maze():
     gen_maze_maps("g19", (19, 120, 12, 6, 16), [3, 4], 3)
 
 
+def main_domain():
+    """Grid side 128 (and lidar_range 64): the oracle and the CPython-stream generator, whose
+    emulated set order had never held more than a 64x64 map's cells, pinned at the top of the
+    accepted domain.  Each file stays under 1 MB."""
+    os.makedirs(OUT, exist_ok=True)
+    gen_inject("g128", 24, 8)
+    gen_inject("g128r64", 24, 9)
+    gen_maps("g128", [0, 5], 3)
+    gen_maze_maps("g128", CONFIGS["g128"], [0, 6], 2)
+    for f in ("inject_g128", "inject_g128r64", "maps_g128", "maze_g128"):
+        size = os.path.getsize(os.path.join(OUT, f + ".npz"))
+        assert size < 1000 * 1000, (f, size)
+        print(f, size, "bytes")
+
+
 def main_mcts():
     os.makedirs(OUT, exist_ok=True)
     gen_mcts("g7", "g7", 30, 40, 4, 40, 500, inject_cases=30)
@@ -745,6 +764,8 @@ if __name__ == "__main__":
         main_mcts()
     elif sys.argv[1:] == ["maze"]:
         main_maze()
+    elif sys.argv[1:] == ["domain"]:
+        main_domain()
     elif sys.argv[1:] == ["rules"]:
         os.makedirs(OUT, exist_ok=True)
         gen_traj_rules()
