@@ -22,7 +22,7 @@ CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in
            ("plantos_batch.hip", "pe_mcts.hip", "pe_render.hip", "pe_pystream.cpp", "pe_policy.hip",
             "pe_policy_host.cpp", "pe_policy_lstm.hip", "pe_rollout.hip", "pe_rollout_host.cpp", "pe_replay.hip",
-            "pe_replay_host.cpp", "pe_policy_bf16.hip")]
+            "pe_replay_host.cpp", "pe_policy_bf16.hip", "pe_learner.hip", "pe_learner_host.cpp")]
 # What a rebuild depends on, by rule: every header beside the sources (lidar_tables.inc, which
 # build() regenerates first, by name too), the C API and the generator of the LIDAR tables.
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in

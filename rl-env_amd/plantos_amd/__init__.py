@@ -12,16 +12,19 @@ Public surface:
                     snapshots of the LSTM state in the Rollout
   RolloutMinibatch  a shuffled minibatch of a Rollout, gathered on the device (SB3's
                     RolloutBuffer.get): Rollout.minibatches / env_minibatches / next_minibatch
+  A2CLearner        SB3's A2C.train() on the device: loss, backward pass through both towers,
+                    clip_grad_norm_ and the RMSpropTFLike step; the policy acts with the new weights
   ReplayCollector   DQN's collection on the device: epsilon-greedy exploration, the transition
                     ring, uniform minibatch sampling (a ReplayBatch) and TD targets
 """
 from .batch import PlantOSBatch  # noqa: F401
+from .learner import A2CLearner  # noqa: F401
 from .policy import Policy, RecurrentPolicy  # noqa: F401
 from .replay import ReplayBatch, ReplayCollector, linear_eps  # noqa: F401
 from .rollout import (RecurrentRolloutCollector, Rollout, RolloutCollector, RolloutMinibatch,  # noqa: F401
                       host_adv_norm, host_minibatch_indices)
 from .vec_env import PlantOSVecEnv, PlantOSVectorEnv  # noqa: F401
 
-__all__ = ["PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy", "Rollout",
+__all__ = ["A2CLearner", "PlantOSBatch", "PlantOSVecEnv", "PlantOSVectorEnv", "Policy", "RecurrentPolicy", "Rollout",
            "RolloutCollector", "RecurrentRolloutCollector", "ReplayBatch", "ReplayCollector", "linear_eps",
            "RolloutMinibatch", "host_minibatch_indices", "host_adv_norm"]

@@ -124,6 +124,21 @@ class PERolloutMb(ctypes.Structure):
     ]
 
 
+class PELearnerPlanInfo(ctypes.Structure):
+    """pe_learner_plan_info (csrc/pe_learner.h): what an A2C learner is made of, without a device."""
+    _fields_ = [("env_tile", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("grad_chunk", ctypes.c_int32),
+                ("max_chunks", ctypes.c_int32), ("wgrad_groups", ctypes.c_int32), ("sum_chunks", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_uint64), ("n_params", ctypes.c_uint64), ("ws_floats", ctypes.c_uint64),
+                ("partial_floats", ctypes.c_uint64), ("sums_doubles", ctypes.c_uint64),
+                ("packed_floats", ctypes.c_uint64), ("packed_t_floats", ctypes.c_uint64)]
+
+
+class PELearnerBufs(ctypes.Structure):
+    """pe_learner_bufs (csrc/pe_learner.h): the device buffers a learner works in."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("params", "grads", "square_avg", "out", "n_updates", "ws", "partials", "sums", "packed", "packed_t")]
+
+
 class PlantOSNativeError(RuntimeError):
     pass
 
@@ -222,6 +237,13 @@ def _signatures():
         "pe_internal_rollout_perm_host": (INT, [I64, U64, U64, I32, I64, I64, P]),
         "pe_internal_rollout_adv_norm": (INT, [I32, I32, I64, P, P, P, P, P]),
         "pe_internal_rollout_adv_norm_host": (INT, [I32, I32, I64, P, P]),
+        # csrc/pe_learner.h
+        "pe_internal_learner_plan": (INT, [I32, I32, I32, I32, TP, I32, I32, ctypes.POINTER(PELearnerPlanInfo)]),
+        "pe_internal_learner_create": (INT, [P, I32, ctypes.POINTER(PELearnerBufs), PP]),
+        "pe_internal_learner_destroy": (INT, [P]),
+        "pe_internal_learner_repack": (INT, [P, P]),
+        "pe_internal_learner_update": (INT, [P, I32, P, I32, P, P, P] + [D] * 6 + [P]),
+        "pe_internal_learner_update_host": (INT, [I32, I32, I32, TP, I32, P, P, P, P] + [D] * 6 + [I32, P, P, P]),
     }
     return abi, internal
 
@@ -229,8 +251,8 @@ def _signatures():
 # name -> (restype, [argtypes]).  SIGNATURES: every function of include/plantos_batch.h
 # (tests/test_capi_symbols.py checks each entry against the header's prototype);
 # INTERNAL_SIGNATURES: the plan entry points of csrc/pe_handle.hpp (with the MCTS stream
-# conversions declared beside pe_internal_mcts_plan) and the rollout minibatches of
-# csrc/pe_rollout_minibatch.h, which are not part of the ABI.
+# conversions declared beside pe_internal_mcts_plan), the rollout minibatches of
+# csrc/pe_rollout_minibatch.h and the A2C learner of csrc/pe_learner.h, which are not part of the ABI.
 SIGNATURES, INTERNAL_SIGNATURES = _signatures()
 EXPORTS = list(SIGNATURES)
 

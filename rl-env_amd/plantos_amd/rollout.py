@@ -7,14 +7,14 @@ gae_lambda=0.95, trainingCode.py:140-162): per-step storage of obs, actions, rew
 starts, values and log-probs, the time-limit bootstrap of truncated episodes and the
 reverse-time GAE scan -- the C-ABI's pe_rollout_record / pe_rollout_gae
 (include/plantos_batch.h, "Rollout collection") around Policy.act and PlantOSBatch.step.
-Learners stay out of scope: the Rollout is the data they consume.
+The Rollout is the data a learner consumes; A2C's learner is plantos_amd.A2CLearner (learner.py).
 
     collector = RolloutCollector(venv, policy, n_steps=5, gamma=0.99, gae_lambda=1.0)
+    learner = A2CLearner(policy, max_rows=5 * venv.num_envs)
     venv.reset()
     while training:
         ro = collector.collect()            # device tensors; no host sync
-        learner.update(ro.obs_f32(), ro.actions, ro.advantages, ro.returns, ro.log_probs, ro.values)
-        policy.load(learner.state_dict())
+        learner.train(ro)                   # A2C.train on the device; the policy acts with the new weights
 
 RecurrentRolloutCollector is the same for a two-tower RecurrentPolicy (sb3_contrib's
 RecurrentPPO.collect_rollouts): the LSTM state advances with the steps, the bootstrap and
