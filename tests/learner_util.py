@@ -8,13 +8,33 @@ from policy_util import make_tensors, obs_rows
 
 NETS = {"n32": [[32, 5], [32, 1]], "n64x32": [[64, 32, 8], [32, 64, 1]], "n96_3x32": [[96, 2], [32, 32, 32, 1]],
         "a2c": [[256, 256, 5], [256, 256, 1]], "w512": [[512, 5], [512, 1]]}
-GEOMETRY = {52: (8, 4), 72: (10, 5), 107: None}  # D -> (G, R) of policy_geometries' e52 / e72; 107: the golden rows
+# Hyper-parameter sets away from the loop's (7e-4, 0.01, 0.5, 0.5, 0.99, 1e-5): the constructor's defaults (SB3's: no
+# entropy bonus), no value loss, and every one moved at once.
+HYPER_SETS = {
+    "defaults": {},
+    "vf0": dict(learning_rate=7e-4, ent_coef=0.01, vf_coef=0.0),
+    "moved": dict(learning_rate=1e-2, ent_coef=0.0, vf_coef=0.25, max_grad_norm=0.1, alpha=0.9, rms_prop_eps=1e-8),
+}
+# D -> (G, R) of policy_geometries' e52 / e72; 107: the golden rows; 57, 87, 127, 347: test_gpu_learner's GEO
+GEOMETRY = {52: (8, 4), 72: (10, 5), 107: None, 57: (9, 3), 87: (12, 7), 127: (12, 5), 347: (24, 6)}
 
 
-def minibatch(towers, D, rows, seed):
-    """(tensors, obs f32 [rows, D], actions i32, advantages f32, returns f32), seeded."""
+def scale_pi_head(tensors, scale):
+    """`tensors` with the pi head's weight matrix (not its bias) multiplied by `scale` in f32: the
+    logit gaps grow by that factor and the softmax saturates.  The inputs are left as they are."""
+    out = [[(w.copy(), b.copy()) for w, b in tw] for tw in tensors]
+    w, b = out[0][-1]
+    out[0][-1] = ((w * np.float32(scale)).astype(np.float32), b)
+    return out
+
+
+def minibatch(towers, D, rows, seed, head_scale=None):
+    """(tensors, obs f32 [rows, D], actions i32, advantages f32, returns f32), seeded.  head_scale:
+    scale_pi_head's factor (None: the tensors as drawn)."""
     rng = np.random.default_rng(1000 + seed)
     tensors = make_tensors(towers, D, seed, scale="var")
+    if head_scale is not None:
+        tensors = scale_pi_head(tensors, head_scale)
     obs = obs_rows(D, rows, seed=seed, geometry=GEOMETRY[D])
     actions = rng.integers(0, towers[0][-1], rows).astype(np.int32)
     adv = rng.standard_normal(rows).astype(np.float32)
